@@ -16,14 +16,26 @@ Inputs are resident in HBM before the timed region; the per-trace plan
 settings (--steps 20 --warmup 5).
 
 Metric: schedule decisions/s (seeds x events / s), whole job.
-Also reported (same JSON line): the roofline of the dominant kernel
-(k_replayable_sweep_oq, HIP events on its launch stream), a CPU baseline
-(the oracle's C restatement on the host cores, bounded sample) and
-secondary lines for the random-policy sweep (configs[3]) and the banded
-edit-distance all-pairs search (configs[2]), each on a per-GPU share.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
-torch.distributed.run (one rank per GPU, RCCL).
+A plain run does only what that figure needs: set-up, warm-up, the K timed
+steps, --dump-outputs if asked, and the result line (metric, value, unit,
+ms_per_step, ...). --dump-outputs DIR writes what the last timed step handed
+its caller (that step's per-seed statistics and top-64, and the job's merged
+top-64) as float64 .npy files; the inputs are the same from run to run, so two
+builds can be compared output for output.
+
+With --full the same JSON line also reports the roofline of the dominant
+kernel (k_replayable_sweep_wt, HIP events on its launch stream), the job's
+top-64 checked against the host merge, a CPU baseline (the oracle's C
+restatement on the host cores, bounded sample), configs[1] end to end, and
+secondary lines for the random-policy sweep (configs[3]), the banded
+edit-distance all-pairs searches (configs[2], configs[4]), the K1 cliffs,
+visualize and configs[0], each on a per-GPU share; the full record goes to
+--full-record.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]
+[--dump-outputs DIR]; for N > 1 under torch.distributed.run (one rank per GPU,
+RCCL).
 """
 import argparse
 import ctypes
@@ -310,10 +322,40 @@ def merge_topk(entries, k):
     return _merge([entries], k)
 
 
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together stay below this
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def records_f64(a):
+    """A structured array (SCHED_STATS_DTYPE, TOPK_DTYPE) as [rows][fields] float64, fields in the dtype's
+    order; every integer below 2^53 is exact (the bench's delay sums stay below 2^40)."""
+    return np.stack([a[f].astype(np.float64) for f in a.dtype.names], axis=1)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array of `arrays` (name -> structured array) to path/<name>.npy as float64. When
+    they would not fit DUMP_MAX_BYTES together, the largest is cut to a fixed sample of its rows (drawn with
+    DUMP_SAMPLE_SEED, ascending; the row numbers go to path/<name>_rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: records_f64(v) for k, v in arrays.items()}
+    big = max(out, key=lambda k: out[k].nbytes)
+    over = sum(v.nbytes for v in out.values()) - DUMP_MAX_BYTES
+    if over > 0:
+        a = out[big]
+        row = a.shape[1] * 8 + 8  # a row and its row number
+        keep = max((a.nbytes - over) // row - 1, 1)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], int(keep), replace=False))
+        out[big] = a[rows]
+        out[big + "_rows"] = rows.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def bench_replayable(args, torch, D, ctx, L, stream):
     from namazu_amd import _lib
     from namazu_amd.explorepolicy import to_csr
     S, E = args.seeds, args.events
+    full = args.full
     hints = zk_hints(E)
     hoff, hb = to_csr(hints)
     # The job: K = args.steps batches of S fresh seeds per rank. Timed step i sweeps the decimal seeds
@@ -330,7 +372,8 @@ def bench_replayable(args, torch, D, ctx, L, stream):
     # 83 us per step with torch pool streams vs 59 with the contexts' own streams (tools/step_ab.py, 200 steps)
     NP = max(1, int(os.environ.get("NMZ_BENCH_PIPELINE", "3")))
     K_TOP = 64
-    csr0 = decimal_csr(D.rank * S, S)  # timed step 0's seeds: the CPU baseline's sample and the end-to-end seeds
+    # timed step 0's seeds: the CPU baseline's sample and the end-to-end seeds (--full)
+    csr0 = decimal_csr(D.rank * S, S) if full else None
     ctxs = [ctx] + [_lib.Context(D.local_rank) for _ in range(NP - 1)]
     plans = []
     t0 = time.time()
@@ -399,21 +442,25 @@ def bench_replayable(args, torch, D, ctx, L, stream):
     torch.cuda.synchronize()
     # the roofline's kernel time: K1 launched back to back on ONE stream (no other stream's kernels beside it, the
     # way rocprofv3 --kernel-trace times a dispatch), HIP events around each K1 launch plus its in-kernel span;
-    # enough launches that the engine clock has ramped (a handful after an idle sync run slow)
+    # enough launches that the engine clock has ramped (a handful after an idle sync run slow). A plain run
+    # keeps the launches, untimed: they are the clock ramp the timed region has always started from
     tot, cnt = ctypes.c_double(), ctypes.c_uint64()
     for _ in range(20):
         sweep(0, spare_lo, d_job.data_ptr())
-    _lib.check(L.nmz_timing_enable(ctx.handle, 1))
-    L.nmz_timing_read(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1)
-    L.nmz_timing_read_span(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1)
+    kern_ms = kern_ms_serial_span = None
+    if full:
+        _lib.check(L.nmz_timing_enable(ctx.handle, 1))
+        L.nmz_timing_read(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1)
+        L.nmz_timing_read_span(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1)
     for _ in range(50):
         sweep(0, spare_lo, d_job.data_ptr())
     torch.cuda.synchronize()
-    _lib.check(L.nmz_timing_read(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1))
-    kern_ms = tot.value / max(cnt.value, 1)
-    _lib.check(L.nmz_timing_read_span(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1))
-    kern_ms_serial_span = tot.value / cnt.value if cnt.value else None
-    _lib.check(L.nmz_timing_enable(ctx.handle, 0))
+    if full:
+        _lib.check(L.nmz_timing_read(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1))
+        kern_ms = tot.value / max(cnt.value, 1)
+        _lib.check(L.nmz_timing_read_span(ctx.handle, b"replayable_sweep", ctypes.byref(tot), ctypes.byref(cnt), 1))
+        kern_ms_serial_span = tot.value / cnt.value if cnt.value else None
+        _lib.check(L.nmz_timing_enable(ctx.handle, 0))
     # the timed region: exactly args.steps pipelined steps + the job's merge; K1's launches record their spans
     # (timing is per context: every slot's context records its own launches)
     for c in ctxs:
@@ -508,24 +555,40 @@ def bench_replayable(args, torch, D, ctx, L, stream):
     # baseline's parity check
     # (N > 1: the rank's own list is that merge, and the job's list the host merge of the gathered rank lists)
     lists = np.frombuffer(d_lists.cpu().numpy().tobytes(), dtype=_lib.TOPK_DTYPE)
-    own = np.frombuffer(d_job.cpu().numpy().tobytes(), dtype=_lib.TOPK_DTYPE)
-    want = merge_topk(b"".join(lists[i * K_TOP:(i + 1) * K_TOP].tobytes() for i in range(args.steps)), K_TOP)
-    job_ok = bool(np.array_equal(want, own))
-    if D.world == 1:
-        job_ok = job_ok and bool(np.array_equal(want, merged))
-    elif not host_merge:
-        job_ok = job_ok and bool(np.array_equal(merge_topk(d_gath.cpu().numpy().tobytes(), K_TOP), merged))
-    sweep(0, D.rank * S, d_job.data_ptr())
-    torch.cuda.synchronize()
-    stats = np.frombuffer(d_stats[0].cpu().numpy().tobytes(), dtype=_lib.SCHED_STATS_DTYPE)
-    seed_lo = [D.rank * S]
-    d_soff = [torch.from_numpy(csr0[0].view(np.int32)).to(dev)]
-    d_sb = [torch.from_numpy(csr0[1]).to(dev)]
+    if args.dump_outputs and D.rank == 0 and args.steps:
+        # what the last timed step handed its caller (this rank's): the statistics of every seed of its range and
+        # its top-64 list, and the job's top-64 the timed region ended with
+        i = args.steps - 1
+        dump_outputs(args.dump_outputs, {
+            "last_step_stats": np.frombuffer(d_stats[i % NP].cpu().numpy().tobytes(), dtype=_lib.SCHED_STATS_DTYPE),
+            "last_step_topk": lists[(i % n_lists) * K_TOP:(i % n_lists + 1) * K_TOP],
+            "job_topk": np.asarray(merged)})
+    job_ok = stats = None
+    if full:
+        own = np.frombuffer(d_job.cpu().numpy().tobytes(), dtype=_lib.TOPK_DTYPE)
+        want = merge_topk(b"".join(lists[i * K_TOP:(i + 1) * K_TOP].tobytes() for i in range(args.steps)), K_TOP)
+        job_ok = bool(np.array_equal(want, own))
+        if D.world == 1:
+            job_ok = job_ok and bool(np.array_equal(want, merged))
+        elif not host_merge:
+            job_ok = job_ok and bool(np.array_equal(merge_topk(d_gath.cpu().numpy().tobytes(), K_TOP), merged))
+        sweep(0, D.rank * S, d_job.data_ptr())
+        torch.cuda.synchronize()
+        stats = np.frombuffer(d_stats[0].cpu().numpy().tobytes(), dtype=_lib.SCHED_STATS_DTYPE)
     for plan in plans:
         L.nmz_replayable_plan_destroy(plan)
     torch.cuda.synchronize()
     for c in ctxs[1:]:
         c.close()
+    res = dict(S=S, E=E, hints=(hoff, hb), seeds=csr0, elapsed=el_max,
+               kern_ms=kern_ms, kern_ms_events=kern_ms_timed, kern_ms_serial_span=kern_ms_serial_span,
+               kern_ms_span=kern_ms_span, enqueue_ms=enq * 1e3, gpu_ms=gpu_ms, host_marks_us=marks, plan_ms=plan_ms,
+               stats=stats, topk=merged, pipeline=NP, job_ok=job_ok, k1_kernel=k1)
+    if not full:
+        return res
+    seed_lo = [D.rank * S]
+    d_soff = [torch.from_numpy(csr0[0].view(np.int32)).to(dev)]
+    d_sb = [torch.from_numpy(csr0[1]).to(dev)]
     # configs[1] as stated, end to end: a new trace's plan (tables built and sorted from host hints) + one
     # 2^20-seed sweep with top-k + the copy of the top-k to the host, per trace
     e2e, e2e_plan, e2e_heads = [], [], []
@@ -648,10 +711,7 @@ def bench_replayable(args, torch, D, ctx, L, stream):
         heads = [int(x) for x in out["seed"][::K_TOP]]
         e2e_native = dict(traces=T, ms_per_trace=float(np.median(ms)), ms_per_trace_runs=ms, top1=heads[:4],
                           agrees=heads == e2e_heads)
-    return dict(S=S, E=E, hints=(hoff, hb), seeds=csr0, elapsed=el_max,
-                kern_ms=kern_ms, kern_ms_events=kern_ms_timed, kern_ms_serial_span=kern_ms_serial_span,
-                kern_ms_span=kern_ms_span, enqueue_ms=enq * 1e3, gpu_ms=gpu_ms, host_marks_us=marks, plan_ms=plan_ms, stats=stats, topk=merged, pipeline=NP, job_ok=job_ok,
-                e2e_s=e2e, e2e_plan_s=e2e_plan, e2e_pipe=e2e_pipe, e2e_native=e2e_native, k1_kernel=k1)
+    return dict(res, e2e_s=e2e, e2e_plan_s=e2e_plan, e2e_pipe=e2e_pipe, e2e_native=e2e_native)
 
 
 def cpu_baseline_replayable(r, args):
@@ -1187,13 +1247,9 @@ def headline_line(args, torch, D, ctx, L, stream):
                                 "statistics (sum, max, argmax, top-64) the sweep covers, bit-exact vs the "
                                 "per-decision oracle; K1 derives them from searches, not event by event",
                    "parallelism": f"seed-range x{D.world}" + (" + RCCL all_gather top-k" if D.world > 1 else "")},
-        "roofline": roofline_valu(r["k1_kernel"], dec_launch, r["kern_ms"]),
-        # a new trace's plan (tables + segment sorts + allocations), median over the end-to-end traces;
         # plan_ms_first_three includes the process's first launches (module load) when the bench starts
-        "plan_ms": float(np.median(r["e2e_plan_s"])) * 1e3,
         "plan_ms_first_three": r["plan_ms"],
         "topk_head": [int(x) for x in r["topk"]["seed"][:4]],
-        "job_topk_equals_merge_of_step_lists": r["job_ok"],
         # host time to enqueue the K steps (the timed region's first part): close to ms_per_step * K means the
         # host's launches, not the GPU, set the step
         "enqueue_ms": r["enqueue_ms"],
@@ -1203,8 +1259,14 @@ def headline_line(args, torch, D, ctx, L, stream):
         "host_marks_us": r["host_marks_us"],  # host clock from the region's start at each step of its end
         "steady_state":"value: one trace's resident plan (built once, before the timed region) sweeps a fresh seed "
                         "range every step, and the job's top-64 is merged on the device (+ RCCL all_gather for N > "
-                        "1) inside the timing; end_to_end below builds a new trace's plan inside the timing",
+                        "1) inside the timing; end_to_end (--full) builds a new trace's plan inside the timing",
     }
+    if not args.full:
+        return line
+    line["roofline"] = roofline_valu(r["k1_kernel"], dec_launch, r["kern_ms"])
+    # a new trace's plan (tables + segment sorts + allocations), median over the end-to-end traces
+    line["plan_ms"] = float(np.median(r["e2e_plan_s"])) * 1e3
+    line["job_topk_equals_merge_of_step_lists"] = r["job_ok"]
     one = {"value": dec_launch / float(np.median(r["e2e_s"])), "unit": "decisions/s",
            "ms_median": float(np.median(r["e2e_s"])) * 1e3, "traces": len(r["e2e_s"]),
            "plan_ms": float(np.median(r["e2e_plan_s"])) * 1e3,
@@ -1315,6 +1377,11 @@ def bench_group(args, torch):
             "plan_ms": plan_ms, "topk_head": [int(x) for x in tk["seed"][:4]],
             "what": "per step: nmz_replayable_group_sweep_decimal -- every shard's sweep + device top-64, the "
                     "per-rank merge, RCCL all_gather, the final merge and the copy to the host"}
+    if args.dump_outputs and args.steps:  # the last step's answer: the group's merged top-64 on the host
+        dump_outputs(args.dump_outputs, {"job_topk": np.asarray(tk)})
+    if not args.full:
+        g.close()
+        return line
     sec = []
     if "random" in args.legs:
         evhash, evclass = config3_trace(10_000)
@@ -1395,6 +1462,13 @@ def main():
     ap.add_argument("--full-record", default=os.path.join("gpurun_out", "bench_full.json"),
                     help="file for the full JSON record (every leg); '' to skip. stdout's last line is the compact "
                          "headline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline's timed steps: its roofline, checks, end-to-end figures and CPU "
+                         "baseline, every secondary leg of --legs, and the full record (--full-record). A run "
+                         "without it times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its per-seed statistics "
+                         "and top-64, and the job's top-64) to DIR/<name>.npy as float64")
     ap.add_argument("--vis-traces", type=int, default=100_000)
     ap.add_argument("--vis-cpu-traces", type=int, default=1000)
     ap.add_argument("--group", action="store_true",
@@ -1407,6 +1481,10 @@ def main():
                          "needs 'replayable'")
     args = ap.parse_args()
     args.legs = set(args.legs.split(","))
+    if not args.full:
+        if "replayable" not in args.legs:
+            ap.error("a run without --full times the headline only: --legs needs 'replayable' (or add --full)")
+        args.full_record = ""
     # The JSON lines are the only output on stdout (one per secondary leg, then the compact headline last):
     # whatever the libraries write to fd 1 during the run
     # (gloo's connection messages, HIP/RCCL diagnostics) goes to stderr instead.
@@ -1435,7 +1513,7 @@ def main():
     line = {}
     if "replayable" in args.legs:
         line = headline_line(args, torch, D, ctx, L, stream)
-    if args.secondary:
+    if args.full and args.secondary:
         ed3 = dict(workload="configs[2] historystorage all-pairs search, clustered (families of 1,024 "
                             "near-duplicate runs)", traces=args.ed_traces, events=2048, band=32, k=8,
                    generator="clustered_traces", gen_kwargs=dict(family=1024), steps=args.ed_steps,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Python-driven trace stream vs the native batch call (nmz_replayable_sweep_traces) on one GPU timeline
 (measurement tooling). Reads a rocprofv3 --kernel-trace --memory-copy-trace database of
-`bench.py --legs replayable` and splits the plan-kernel launches into runs of T consecutive builds: the last run
+`bench.py --full --legs replayable` and splits the plan-kernel launches into runs of T consecutive builds: the last run
 is the last native batch call, the fourth from the end the native warm-up call, the fifth the timed Python stream
 (the bench makes the timed stream, then a warm-up and three timed native calls). Prints, per run: span, busy
 time, per-kernel totals and the streams used.

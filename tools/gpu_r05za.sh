@@ -9,7 +9,7 @@ rc=$?; tail -2 $O/tests.log; [ $rc -eq 0 ] || exit $rc
 for rep in 1 2; do
 for v in masks ballots; do
   if [ $v = masks ]; then E=""; else E="NMZ_AB=1 NMZ_SIG_MASKS=0"; fi
-  env $E timeout -k 10 200 python bench.py --legs visualize --no-cpu-baseline --full-record $O/${v}_$rep.json > /dev/null 2> $O/${v}_$rep.err || exit $?
+  env $E timeout -k 10 200 python bench.py --full --legs visualize --no-cpu-baseline --full-record $O/${v}_$rep.json > /dev/null 2> $O/${v}_$rep.err || exit $?
   python3 -c "
 import json;d=json.load(open('$O/${v}_$rep.json'))
 s=d['secondary'][0]
