@@ -20,6 +20,10 @@
  *                             Intn(999) fault draw), batched over seeds x events
  *                             under the deterministic per-event seeding contract
  *                             documented in DESIGN.md section 2.
+ *   nmz_procset_*          -> Random's procPolicy.Action for ProcSetEvents
+ *                             randompolicy.go:300-304, mild.go:44-57, extreme.go:44-63,
+ *                             dirichlet.go:58-82 (one scheduling attribute per process),
+ *                             on the host, on the device, and batched over seeds x events.
  *   nmz_random_params_resolve -> Random.LoadConfig's interval/probability
  *                             semantics randompolicy.go:156-228,332-340.
  *   nmz_ed_pairs / nmz_ed_allpairs_knn -> HistoryStorage similarity search
@@ -110,7 +114,7 @@ int nmz_device_count(int *count);
 int nmz_ctx_stream(nmz_ctx *ctx, void **stream);
 
 /* Kernel timing (HIP events recorded on the launch stream around the dominant
- * kernels: "replayable_sweep", "random_sweep", "ed_tile"). on = 0 off, 1 events and
+ * kernels: "replayable_sweep", "random_sweep", "procset_sweep", "ed_tile"). on = 0 off, 1 events and
  * spans, NMZ_TIMING_SPANS (2) the kernels' own spans only (no event records between a
  * stream's launches: each record is a marker the queue waits on, ~6 us). */
 #define NMZ_TIMING_SPANS 2
@@ -296,6 +300,95 @@ int nmz_random_plan_create(nmz_ctx *ctx, const uint64_t *evhash, const uint8_t *
 int nmz_random_plan_destroy(nmz_random_plan *plan);
 int nmz_random_sweep_dev(nmz_random_plan *plan, uint64_t seed0, uint64_t n_seeds,
                          nmz_sched_stats *d_stats, void *stream);
+
+/* ---- random policy: ProcSetEvent decisions (procPolicy) -----------------------
+ * makeActionForEvent hands every ProcSetEvent to the policy's procPolicy
+ * (randompolicy.go:300-304), which answers with a ProcSetSchedAction: one
+ * scheduling attribute per process of the set. The decision for (seed s, event e)
+ * uses the generator of nmz_random_sweep and draws, in order,
+ *   1. the delay, exactly as nmz_random_sweep (QueueEvent treats the event like any
+ *      other; a ProcSetEvent is not deferred, so there is no fault draw);
+ *   2. with n = n_procs[e], the sub-policy's draws:
+ *      mild      (mild.go:44-57)     slot i: nice = -20 + Int31n(40); policy SCHED_BATCH
+ *                                    if use_batch, else SCHED_NORMAL;
+ *      extreme   (extreme.go:44-63)  `prioritized` times: mark slot Int31n(n) (a set);
+ *                                    then, in slot order, a marked slot is
+ *                                    {SCHED_RR, priority = Int31n(10)}, the others
+ *                                    {SCHED_BATCH}; prioritized <= 0: no draws;
+ *      dirichlet (dirichlet.go:58-82) slot i: reset = Intn(999) < reset_threshold;
+ *                                    a reset slot is {SCHED_NORMAL}, the others
+ *                                    {SCHED_DEADLINE, SCHED_FLAG_RESET_ON_FORK}. The
+ *                                    runtime ratios come from a second, clock-seeded
+ *                                    generator (dirichlet.go:29-31) and are not part
+ *                                    of this interface.
+ * Limits (the closed forms cover 607 generator outputs): n_procs[e] <= 512 and
+ * prioritized <= 256, NMZ_EINVAL beyond; extreme with n = 0 and prioritized > 0
+ * (Go's Int31n(0) panics) and dirichlet with n = 0 ("has no process", dirichlet.go:43-45)
+ * are NMZ_EINVAL. evclass may carry NMZ_EV_PRIORITIZED only. */
+#define NMZ_PROC_MILD 0
+#define NMZ_PROC_EXTREME 1
+#define NMZ_PROC_DIRICHLET 2
+#define NMZ_PROCSET_MAX_PROCS 512
+#define NMZ_PROCSET_MAX_PRIORITIZED 256
+
+typedef struct nmz_procset_params {
+    int32_t policy;          /* NMZ_PROC_*                                              */
+    int32_t use_batch;       /* PPPMild.UseBatch                                        */
+    int32_t prioritized;     /* PPPExtreme.Prioritized                                  */
+    int32_t reset_threshold; /* int(PPPDirichlet.ResetProbability * 1000.0)             */
+} nmz_procset_params;
+
+/* loadProcConfig's checks (randompolicy.go:230-270): proc_policy "" or NULL means mild; errors
+ * "bad procPolicy %s" and "bad procPolicyParam.resetProbability %f" (:262-267); prioritized above
+ * NMZ_PROCSET_MAX_PRIORITIZED is NMZ_EINVAL. Host only. */
+int nmz_procset_params_resolve(const char *proc_policy, int use_batch, int prioritized, double reset_probability,
+                               nmz_procset_params *out);
+
+/* One process's attribute, 16 bytes; policy and flags are the Linux numbers (linuxsched.SchedAttr):
+ * SCHED_NORMAL 0, SCHED_RR 2, SCHED_BATCH 3, SCHED_DEADLINE 6; SCHED_FLAG_RESET_ON_FORK 1. */
+typedef struct nmz_proc_attr {
+    uint32_t policy;
+    int32_t nice;
+    uint32_t priority;
+    uint32_t flags;
+} nmz_proc_attr;
+
+/* Per-seed statistics of a ProcSet sweep, 32 bytes. The favour score of one process in one decision (higher =
+ * more CPU): mild -nice (-19..20); extreme 1 + priority if SCHED_RR, else 0; dirichlet 1 if reset, else 0. */
+typedef struct nmz_procset_stats {
+    uint64_t sum_delay_ns; /* sum of delays, mod 2^64                                          */
+    int64_t score_sum;     /* favour score over every process of every event                    */
+    int64_t target_score;  /* favour score over target_slot[e] of every event                   */
+    uint32_t n_special;    /* mild: processes with nice < 0; extreme: SCHED_RR; dirichlet: resets */
+    uint32_t flags;        /* NMZ_STAT_* bits                                                   */
+} nmz_procset_stats;
+
+typedef struct nmz_procset_topk_entry {
+    uint64_t seed;
+    int64_t target_score;
+} nmz_procset_topk_entry;
+
+/* procPolicy.Action (mild.go:30-40, extreme.go:30-40, dirichlet.go:38-51) for one seed on the calling thread, no
+ * device work: delays[n_events] and attrs[sum of n_procs], event e's processes at the prefix sum of n_procs[0..e).
+ * Shares its decision code with the kernels, as nmz_random_decide_host does. */
+int nmz_procset_decide_host(uint64_t seed, const uint64_t *evhash, const uint8_t *evclass, const uint32_t *n_procs,
+                            uint32_t n_events, const nmz_random_params *random_params,
+                            const nmz_procset_params *procset_params, int64_t *delays, nmz_proc_attr *attrs);
+/* The same decisions (same reference lines) on the device, one thread per event. Synchronous. */
+int nmz_procset_decide(nmz_ctx *ctx, uint64_t seed, const uint64_t *evhash, const uint8_t *evclass,
+                       const uint32_t *n_procs, uint32_t n_events, const nmz_random_params *random_params,
+                       const nmz_procset_params *procset_params, int64_t *delays, nmz_proc_attr *attrs);
+/* procPolicy.Action (the same reference lines) batched over seeds seed0 .. seed0 + n_seeds - 1 (wrapping past 2^64 as
+ * nmz_random_sweep) x events. target_slot[e] is a slot < n_procs[e] or NMZ_NONE; NULL = all NMZ_NONE.
+ * Outputs (each may be NULL): stats[n_seeds]; delays[n_dump_seeds * n_events] and attrs[n_dump_seeds * sum of
+ * n_procs] (row-major, one row per seed, laid out as nmz_procset_decide_host's) for the first n_dump_seeds seeds;
+ * topk[k], k <= 256, by target_score (descending if `descending`, else ascending), then seed ascending, .seed = the
+ * seed value; entries past n_seeds are {UINT64_MAX, INT64_MIN}. */
+int nmz_procset_sweep(nmz_ctx *ctx, uint64_t seed0, uint64_t n_seeds, const uint64_t *evhash, const uint8_t *evclass,
+                      const uint32_t *n_procs, const uint32_t *target_slot, uint32_t n_events,
+                      const nmz_random_params *random_params, const nmz_procset_params *procset_params,
+                      nmz_procset_stats *stats, int64_t *delays, nmz_proc_attr *attrs, uint64_t n_dump_seeds,
+                      uint32_t k, int descending, nmz_procset_topk_entry *topk);
 
 /* Top-k selection over device-resident stats (seed value = seed0 + index).
  * k <= 256 (here and for the sweeps' topk outputs); NMZ_EINVAL otherwise. */

@@ -28,6 +28,8 @@ NMZ_NONE = 0xFFFFFFFF
 NMZ_ED_NCOUNTERS = 6
 NMZ_ED_OPT_SINGLE_KERNEL, NMZ_ED_OPT_NO_QGRAM, NMZ_ED_OPT_COMPACT, NMZ_ED_OPT_HOST_BUILD = 1, 2, 4, 8
 NMZ_ED_FP_WORDS = 8
+NMZ_PROC_MILD, NMZ_PROC_EXTREME, NMZ_PROC_DIRICHLET = 0, 1, 2
+NMZ_PROCSET_MAX_PROCS, NMZ_PROCSET_MAX_PRIORITIZED = 512, 256
 
 SCHED_STATS_DTYPE = np.dtype([
     ("sum_delay_ns", "<u8"), ("max_delay_ns", "<i8"), ("argmax_event", "<u4"),
@@ -36,6 +38,14 @@ assert SCHED_STATS_DTYPE.itemsize == 32
 TOPK_DTYPE = np.dtype([("seed", "<u8"), ("sum_delay_ns", "<i8"), ("n_fault", "<u4"),
                        ("first_fault", "<u4")])
 assert TOPK_DTYPE.itemsize == 24
+# ProcSetEvent decisions (nmz_proc_attr, nmz_procset_stats, nmz_procset_topk_entry)
+PROC_ATTR_DTYPE = np.dtype([("policy", "<u4"), ("nice", "<i4"), ("priority", "<u4"), ("flags", "<u4")])
+assert PROC_ATTR_DTYPE.itemsize == 16
+PROCSET_STATS_DTYPE = np.dtype([("sum_delay_ns", "<u8"), ("score_sum", "<i8"), ("target_score", "<i8"),
+                                ("n_special", "<u4"), ("flags", "<u4")])
+assert PROCSET_STATS_DTYPE.itemsize == 32
+PROCSET_TOPK_DTYPE = np.dtype([("seed", "<u8"), ("target_score", "<i8")])
+assert PROCSET_TOPK_DTYPE.itemsize == 16
 
 
 class NmzLibraryError(RuntimeError):
@@ -55,6 +65,11 @@ class NmzInvalidArgument(NmzError, ValueError):
 class RandomParams(ctypes.Structure):
     _fields_ = [("min_ns", ctypes.c_int64 * 2), ("max_ns", ctypes.c_int64 * 2),
                 ("fault_threshold", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class ProcSetParams(ctypes.Structure):
+    _fields_ = [("policy", ctypes.c_int32), ("use_batch", ctypes.c_int32), ("prioritized", ctypes.c_int32),
+                ("reset_threshold", ctypes.c_int32)]
 
 
 # every entry point declared in include/nmz_gpu.h: name -> (restype, argtypes)
@@ -84,6 +99,10 @@ SIGNATURES = {
     "nmz_replayable_decide": (_int, [_P, _P, _u32, _P, _P, _u32, _i64, _P]),
     "nmz_random_decide": (_int, [_P, _u64, _P, _P, _u32, _P, _P, _P]),
     "nmz_random_sweep": (_int, [_P, _u64, _u64, _P, _P, _u32, _P, _P, _P, _P, _u64, _u32, _P]),
+    "nmz_procset_params_resolve": (_int, [ctypes.c_char_p, _int, _int, ctypes.c_double, _P]),
+    "nmz_procset_decide_host": (_int, [_u64, _P, _P, _P, _u32, _P, _P, _P, _P]),
+    "nmz_procset_decide": (_int, [_P, _u64, _P, _P, _P, _u32, _P, _P, _P, _P]),
+    "nmz_procset_sweep": (_int, [_P, _u64, _u64, _P, _P, _P, _P, _u32, _P, _P, _P, _P, _P, _u64, _u32, _int, _P]),
     "nmz_random_plan_create": (_int, [_P, _P, _P, _u32, _P, _u64, ctypes.POINTER(_P)]),
     "nmz_random_plan_destroy": (_int, [_P]),
     "nmz_random_sweep_dev": (_int, [_P, _u64, _u64, _P, _P]),
@@ -205,6 +224,15 @@ def resolve_random_params(min_ns, max_ns, probability):
     p = RandomParams()
     check(load().nmz_random_params_resolve(int(min_ns), int(max_ns), float(probability),
                                            ctypes.byref(p)))
+    return p
+
+
+def resolve_procset_params(proc_policy="mild", use_batch=True, prioritized=3, reset_probability=0.1):
+    """nmz_procset_params_resolve: loadProcConfig's checks (randompolicy.go:230-270) and the kernels' integers."""
+    p = ProcSetParams()
+    name = None if proc_policy is None else str(proc_policy).encode()
+    check(load().nmz_procset_params_resolve(name, int(bool(use_batch)), int(prioritized), float(reset_probability),
+                                            ctypes.byref(p)))
     return p
 
 

@@ -20,66 +20,12 @@
 #include "go_rand.h"
 #include "nmz_common.h"
 #include "nmz_internal.h"
+#include "random_dev.h"
 
 namespace nmz {
 
-constexpr uint64_t MASK63 = 0x7fffffffffffffffULL;
 constexpr uint32_t INTN_N = 999;
 constexpr uint32_t INT31N_MAX = 0x7fffffffu - (0x80000000u % INTN_N);  // rand.go Int31n
-
-__constant__ uint64_t d_cooked[gorand::LEN] = NMZ_GO_RNG_COOKED_INIT;
-[[maybe_unused]] __device__ const gorand::PowTable d_powa = gorand::make_pow_table();
-// the same tables for the host decision path (nmz_random_decide_host): the decision code below is shared
-[[maybe_unused]] static constexpr gorand::PowTable h_powa = gorand::make_pow_table();
-[[maybe_unused]] static constexpr uint64_t h_cooked[gorand::LEN] = NMZ_GO_RNG_COOKED_INIT;
-#ifdef __HIP_DEVICE_COMPILE__
-#define NMZ_POWA(i) d_powa.v[i]
-#define NMZ_COOKED(i) d_cooked[i]
-#else
-#define NMZ_POWA(i) h_powa.v[i]
-#define NMZ_COOKED(i) h_cooked[i]
-#endif
-
-// seeded vec[p] for a runtime index (slow path)
-__host__ __device__ uint64_t vec_rt(uint32_t s, int p) {
-    const uint32_t xa = gorand::modmul(s, NMZ_POWA(21 + 3 * p));
-    const uint32_t xb = gorand::modmul(s, NMZ_POWA(22 + 3 * p));
-    const uint32_t xc = gorand::modmul(s, NMZ_POWA(23 + 3 * p));
-    const uint64_t ck = NMZ_COOKED(p);
-    const uint32_t lo = (xb << 20) ^ xc ^ (uint32_t)ck;
-    const uint32_t hi = (xa << 8) ^ (xb >> 12) ^ (uint32_t)(ck >> 32);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// y_t for 0 <= t < 607: y_t = y_{t-607} + y_{t-273}, y_s (s<0) = vec[(333-s) mod 607]
-__host__ __device__ uint64_t go_output(uint32_t s, int t) {
-    uint64_t acc = 0;
-    int u = t;
-    while (u >= 0) {
-        acc += vec_rt(s, (333 - (u - 607)) % 607);
-        u -= 273;
-    }
-    return acc + vec_rt(s, ((333 - u) % 607 + 607) % 607);
-}
-
-struct ClassParams {
-    int64_t min;
-    uint64_t n;          // max - min (0 => fixed duration, no draw)
-    uint64_t max_accept; // Int63n rejection bound
-    uint64_t mu;         // floor(2^64 / n) (Barrett), 0 if n is a power of two
-};
-
-struct RandomKParams {
-    ClassParams cls[2];
-    int32_t fault_threshold;
-};
-
-// v mod n for v < 2^63, n not a power of two, mu = floor(2^64/n)
-__host__ __device__ __forceinline__ uint64_t mod_barrett(uint64_t v, uint64_t n, uint64_t mu) {
-    const uint64_t q = umulhi64(v, mu);
-    uint64_t r = v - q * n;
-    return r >= n ? r - n : r;
-}
 
 struct Decision {
     int64_t delay;
@@ -183,28 +129,6 @@ __device__ __forceinline__ Decision decide_sweep(uint32_t s, uint32_t cls, const
     return d;
 }
 
-__device__ __forceinline__ uint4 uniform4(uint4 v) {
-    return make_uint4(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y),
-                      __builtin_amdgcn_readfirstlane(v.z), __builtin_amdgcn_readfirstlane(v.w));
-}
-
-// Go seed for (prefix state h0 -> H = h0 * P^8, its residue Hm = H mod M31) and
-// one table entry q = {C lo, C hi, C mod M31, class}
-// nm = -M31 and one = 1 arrive in VGPRs the compiler cannot see through, so that both conditional corrections are
-// a VOP2 borrow (v_sub_co) plus a VCC v_cndmask with VGPR operands (full rate) rather than an add of a literal and
-// a v_min_u32 (half rate), and the s == 0 test is a borrow out of s - 1 rather than a v_cmp.
-__device__ __forceinline__ uint32_t go_seed_from_table(uint64_t H, uint32_t Hm, uint4 q,
-                                                       uint32_t nm = gorand::NEG_M31, uint32_t one = 1u) {
-    const uint64_t C = ((uint64_t)q.y << 32) | q.x;
-    const uint64_t u = H + C;
-    const uint32_t k = (uint32_t)(u < H) + (uint32_t)(u >> 63);  // wrap carry + sign
-    uint32_t s1 = Hm + q.z, t;                                   // < 2*M31
-    s1 = __builtin_sub_overflow(s1, 0u - nm, &t) ? s1 : t;
-    uint32_t dd;
-    const uint32_t s = __builtin_sub_overflow(s1, 4u * k, &dd) ? dd - nm : dd;
-    return __builtin_sub_overflow(s, one, &t) ? 89482311u : s;
-}
-
 // per-event table: FNV correction for hint = le64(evhash), class bits
 __global__ __launch_bounds__(256) void k_random_table(const uint64_t *__restrict__ evhash,
                                                       const uint8_t *__restrict__ evclass, uint32_t E,
@@ -217,13 +141,6 @@ __global__ __launch_bounds__(256) void k_random_table(const uint64_t *__restrict
     const uint64_t C = h - (uint64_t)L * fnv_pow(8);
     table[(uint64_t)L * E + e] = make_uint4((uint32_t)C, (uint32_t)(C >> 32), (uint32_t)(C % gorand::M31),
                                             evclass[e]);
-}
-
-__host__ __device__ __forceinline__ uint64_t seed_prefix(uint64_t seed) {
-    uint64_t h = FNV_OFFSET;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h = fnv_step(h, (uint32_t)(seed >> (8 * i)) & 0xff);
-    return h;
 }
 
 __global__ __launch_bounds__(256) void k_random_prefix(uint64_t seed0, uint64_t n, uint64_t *__restrict__ h0,
@@ -424,20 +341,9 @@ __global__ __launch_bounds__(256) void k_random_decide(uint64_t seed, const uint
 
 }  // namespace nmz
 
-struct nmz_random_plan {
-    nmz_ctx *ctx = nullptr;
-    uint32_t n_events = 0;
-    nmz::RandomKParams kp{};
-    uint4 *d_table = nullptr;
-    uint64_t max_seeds = 0;
-    nmz::DevBuf table_mem;
-    nmz::DevBuf seed_scratch;
-    nmz::DevBuf partial;  // per-chunk partial stats per seed slot (n_chunks > 1)
-};
-
 namespace nmz {
 
-static int make_kparams(const nmz_random_params *p, RandomKParams &kp) {
+int make_kparams(const nmz_random_params *p, RandomKParams &kp) {
     NMZ_CHECK(p != nullptr, "params is NULL");
     std::memset(&kp, 0, sizeof kp);
     for (int i = 0; i < 2; ++i) {
@@ -495,13 +401,13 @@ static Buckets carve_random(void *p, uint64_t S, uint64_t **h0, uint32_t **count
     return b;
 }
 
-static int random_plan_create(nmz_ctx *ctx, const uint64_t *evhash, const uint8_t *evclass, uint32_t E,
+int random_plan_create(nmz_ctx *ctx, const uint64_t *evhash, const uint8_t *evclass, uint32_t E,
                               const nmz_random_params *params, uint64_t max_seeds, nmz_random_plan **out) {
     NMZ_CHECK(ctx && out, "NULL argument");
     NMZ_CHECK(E == 0 || (evhash && evclass), "evhash/evclass is NULL");
     for (uint32_t e = 0; e < E; ++e)
         NMZ_CHECK((evclass[e] & ~(NMZ_EV_PRIORITIZED | NMZ_EV_FAULTABLE)) == 0,
-                  "evclass has unknown bits (ProcSetEvent decisions are out of scope)");
+                  "evclass has unknown bits (ProcSetEvent decisions: nmz_procset_decide[_host], nmz_procset_sweep)");
     RandomKParams kp;
     NMZ_TRY(make_kparams(params, kp));
     auto *p = new nmz_random_plan();
@@ -537,16 +443,28 @@ static int random_plan_create(nmz_ctx *ctx, const uint64_t *evhash, const uint8_
     return NMZ_OK;
 }
 
+void random_plan_free(nmz_random_plan *p) {
+    p->table_mem.release();
+    p->seed_scratch.release();
+    p->partial.release();
+    delete p;
+}
+
+int random_bucket(nmz_random_plan *p, hipStream_t st, uint64_t seed0, uint64_t S, Buckets &b, uint32_t **counter) {
+    NMZ_CHECK(S <= p->max_seeds, "more seeds than the plan was created for");
+    uint64_t *d_h0;
+    b = carve_random(p->seed_scratch.ptr, p->max_seeds, &d_h0, counter);
+    hipLaunchKernelGGL(k_random_prefix, dim3(ceil_div(S, BUCKET_BLK)), dim3(256), 0, st, seed0, S, d_h0, b.hist);
+    return bucket_seeds_counted(st, d_h0, S, 64, b, *counter);
+}
+
 static int random_run(nmz_random_plan *p, hipStream_t st, uint64_t seed0, uint64_t S, nmz_sched_stats *d_stats) {
     if (S == 0) return NMZ_OK;
-    NMZ_CHECK(S <= p->max_seeds, "more seeds than the plan was created for");
     const uint32_t E = p->n_events;
-    uint64_t *d_h0;
     uint32_t *d_counter;
-    Buckets b = carve_random(p->seed_scratch.ptr, p->max_seeds, &d_h0, &d_counter);
-    hipLaunchKernelGGL(k_random_prefix, dim3(ceil_div(S, BUCKET_BLK)), dim3(256), 0, st, seed0, S, d_h0, b.hist);
+    Buckets b;
+    NMZ_TRY(random_bucket(p, st, seed0, S, b, &d_counter));
     const uint64_t max_units = S / 64 + 256;
-    NMZ_TRY(bucket_seeds_counted(st, d_h0, S, 64, b, d_counter));
     const uint32_t ec = random_ec(S);
     const uint32_t n_chunks = std::max<uint32_t>(1, (E + ec - 1) / ec);
     const uint64_t stride = (p->max_seeds / 64 + 257) * 64;
@@ -692,7 +610,7 @@ int nmz_random_decide_host(uint64_t seed, const uint64_t *evhash, const uint8_t 
     for (uint32_t e = 0; e < n_events; ++e) {
         const uint32_t cls = evclass[e];
         NMZ_CHECK((cls & ~(NMZ_EV_PRIORITIZED | NMZ_EV_FAULTABLE)) == 0,
-                  "evclass has unknown bits (ProcSetEvent decisions are out of scope)");
+                  "evclass has unknown bits (ProcSetEvent decisions: nmz_procset_decide[_host], nmz_procset_sweep)");
         uint64_t h = h0;
         for (int i = 0; i < 8; ++i) h = fnv_step(h, (uint32_t)(evhash[e] >> (8 * i)) & 0xff);
         const Decision d = decide(gorand::seed_reduce((int64_t)h), cls, kp.cls[cls & NMZ_EV_PRIORITIZED],
@@ -717,7 +635,7 @@ int nmz_random_decide(nmz_ctx *ctx, uint64_t seed, const uint64_t *evhash, const
     NMZ_CHECK(evhash && evclass && delays && faults, "NULL argument");
     for (uint32_t e = 0; e < n_events; ++e)
         NMZ_CHECK((evclass[e] & ~(NMZ_EV_PRIORITIZED | NMZ_EV_FAULTABLE)) == 0,
-                  "evclass has unknown bits (ProcSetEvent decisions are out of scope)");
+                  "evclass has unknown bits (ProcSetEvent decisions: nmz_procset_decide[_host], nmz_procset_sweep)");
     hipStream_t st = ctx->stream;
     NMZ_TRY(ctx->buf[9].ensure(Carve::bytes_for(n_events, 8) * 2 + Carve::bytes_for(n_events, 1) * 2 +
                                Carve::bytes_for(4, 4)));

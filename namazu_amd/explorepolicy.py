@@ -35,12 +35,13 @@ import os
 import queue
 import threading
 import time
+import types
 
 import numpy as np
 
 from . import _lib
 from .config import Config
-from .signal import Event
+from .signal import (PROCSET_CLASS, SCHED_DEADLINE, Event, ProcSetSchedAction, sched_attr)
 
 # ----------------------------------------------------------------- registry
 _policy_factories = {}
@@ -76,11 +77,12 @@ def to_csr(items):
 class SweepResult:
     """Per-seed statistics (+ optional per-decision dump and top-k)."""
 
-    def __init__(self, stats, delays=None, faults=None, topk=None):
+    def __init__(self, stats, delays=None, faults=None, topk=None, attrs=None):
         self.stats = stats
         self.delays = delays
         self.faults = faults
         self.topk = topk
+        self.attrs = attrs  # ProcSet sweeps: the dumped seeds' per-process attributes
 
 
 class ChannelClosed(queue.Empty):
@@ -503,6 +505,13 @@ class Random(ExplorePolicy):
     each decision uses a fresh rand.New(rand.NewSource(FNV1a64(le64(seed) ||
     le64(evhash)))) and draws delay first, then fault. The optional "seed"
     parameter fixes the seed; without it one is drawn from os.urandom.
+
+    A ProcSetEvent goes to the procPolicy (mild, extreme or dirichlet; randompolicy.go:300-304), which answers with
+    a ProcSetSchedAction. Under the same contract its decision draws the delay and then the sub-policy's draws
+    (nmz_procset_*). Only these are deterministic: dirichlet's Runtime values come, in the reference, from a second
+    generator seeded from the wall clock (dirichlet.go:29-31); here they come from numpy's Generator.dirichlet seeded
+    from Seed, with os.cpu_count() for runtime.NumCPU(), and are outside the determinism contract -- the reset
+    flags (which processes return to SCHED_NORMAL) are inside it.
     """
 
     NAME = "random"
@@ -516,10 +525,14 @@ class Random(ExplorePolicy):
         self.ShellActionCommand = ""
         self.FaultActionProbability = 0.0
         self.ProcPolicy = "mild"
+        # randompolicy.go:107-117 defaults
+        self.PPPMild = types.SimpleNamespace(UseBatch=True)
+        self.PPPExtreme = types.SimpleNamespace(Prioritized=3)
+        self.PPPDirichlet = types.SimpleNamespace(ResetProbability=0.1)
         self.Seed = int.from_bytes(os.urandom(8), "little")
 
     def LoadConfig(self, cfg: Config):
-        """randompolicy.go:156-228 (ProcSet sub-policies are out of scope)."""
+        """randompolicy.go:156-270 (loadProcConfig: the selected procPolicy's parameter only, as the reference)."""
         try:
             epp = "explorepolicyparam."
             if cfg.is_set(epp + "minInterval"):
@@ -548,9 +561,17 @@ class Random(ExplorePolicy):
                 self.ProcPolicy = pp
             if self.ProcPolicy not in ("mild", "extreme", "dirichlet"):
                 return ValueError(f"bad procPolicy {self.ProcPolicy}")
-            if self.ProcPolicy == "dirichlet":
-                rp = cfg.get_float64(epp + "procPolicyParam.resetProbability") \
-                    if cfg.is_set(epp + "procPolicyParam.resetProbability") else 0.1
+            ppp = epp + "procPolicyParam."
+            if self.ProcPolicy == "mild":
+                if cfg.is_set(ppp + "useBatch"):
+                    self.PPPMild.UseBatch = cfg.get_bool(ppp + "useBatch")
+            elif self.ProcPolicy == "extreme":
+                if cfg.is_set(ppp + "prioritized"):
+                    self.PPPExtreme.Prioritized = cfg.get_int(ppp + "prioritized")
+            else:
+                if cfg.is_set(ppp + "resetProbability"):
+                    self.PPPDirichlet.ResetProbability = cfg.get_float64(ppp + "resetProbability")
+                rp = self.PPPDirichlet.ResetProbability
                 if rp < 0.0 or rp > 1.0:
                     return ValueError(f"bad procPolicyParam.resetProbability {rp:f}")
         except ValueError as e:
@@ -561,6 +582,114 @@ class Random(ExplorePolicy):
         """Resolved integer parameters (x0.8 prioritized intervals, fault threshold)."""
         return _lib.resolve_random_params(self.MinInterval, self.MaxInterval,
                                           self.FaultActionProbability)
+
+    def procset_params(self):
+        """The procPolicy and its parameter as the kernels take them (nmz_procset_params_resolve)."""
+        return _lib.resolve_procset_params(self.ProcPolicy, self.PPPMild.UseBatch, self.PPPExtreme.Prioritized,
+                                           self.PPPDirichlet.ResetProbability)
+
+    @staticmethod
+    def parse_procset_event(event):
+        """parseProcSetEvent (explorepolicy/random/util.go:27-48): the event's process list, with its errors."""
+        opt = event.JSONMap().get("option")
+        xprocs = opt.get("procs") if isinstance(opt, dict) else None
+        if not isinstance(xprocs, (list, tuple)):
+            raise ValueError(f"no procs? this should be an implementation error. event={event.JSONMap()!r}")
+        for x in xprocs:
+            if not isinstance(x, str):
+                raise ValueError("non-string proc? this should be an implementation error. "
+                                 f"xproc={x!r}, event={event.JSONMap()!r}")
+        return list(xprocs)
+
+    def procset_inputs(self, events, target_pid=None):
+        """ProcSetEvents -> (evhash uint64[E], evclass uint8[E], n_procs uint32[E], target_slot uint32[E], procs):
+        the inputs of nmz_procset_*. target_slot[e] is target_pid's slot in event e (the last one when the pid is
+        listed twice: the later slot's attribute is the one the reference's map keeps), NMZ_NONE where it is absent.
+        The event hashes are computed on the host (nmz_fnv1a64_batch_host)."""
+        procs = [self.parse_procset_event(ev) for ev in events]
+        n = len(events)
+        evhash = np.zeros(n, np.uint64)
+        if n:
+            off, data = to_csr([ev.canonical_json() for ev in events])
+            off64 = off.astype(np.uint64)
+            _lib.check(_lib.load().nmz_fnv1a64_batch_host(_lib.ptr(off64), _lib.ptr(data), n, _lib.ptr(evhash)))
+        evclass = np.array([_lib.NMZ_EV_PRIORITIZED if ev.EntityID() in self.PrioritizedEntities else 0
+                            for ev in events], np.uint8)
+        n_procs = np.array([len(p) for p in procs], np.uint32)
+        target = np.full(n, _lib.NMZ_NONE, np.uint32)
+        if target_pid is not None:
+            for i, p in enumerate(procs):
+                if target_pid in p:
+                    target[i] = len(p) - 1 - p[::-1].index(target_pid)
+        return evhash, evclass, n_procs, target, procs
+
+    def ProcSetSweep(self, seed0, n_seeds, evhash, evclass, n_procs, target_slot=None, n_dump=0, k=0,
+                     descending=True, ctx=None):
+        """Every ProcSetEvent decision of seeds seed0..seed0+n_seeds-1 over one trace, on the GPU
+        (nmz_procset_sweep): stats (_lib.PROCSET_STATS_DTYPE) per seed, delays[n_dump, E] and
+        attrs[n_dump, sum(n_procs)] (_lib.PROC_ATTR_DTYPE) of the first n_dump seeds, and the k seeds that favour
+        (descending) or starve (ascending) the target slots the hardest (_lib.PROCSET_TOPK_DTYPE)."""
+        ctx = ctx or self._ctx()
+        evhash = np.ascontiguousarray(evhash, np.uint64)
+        evclass = np.ascontiguousarray(evclass, np.uint8)
+        n_procs = np.ascontiguousarray(n_procs, np.uint32)
+        target = None if target_slot is None else np.ascontiguousarray(target_slot, np.uint32)
+        e, total = len(evhash), int(n_procs.sum())
+        rp, pp = self.params(), self.procset_params()
+        stats = np.zeros(n_seeds, _lib.PROCSET_STATS_DTYPE)
+        delays = np.zeros((n_dump, e), np.int64) if n_dump else None
+        attrs = np.zeros((n_dump, total), _lib.PROC_ATTR_DTYPE) if n_dump else None
+        topk = np.zeros(k, _lib.PROCSET_TOPK_DTYPE) if k else None
+        _lib.check(_lib.load().nmz_procset_sweep(
+            ctx.handle, int(seed0), int(n_seeds), _lib.ptr(evhash), _lib.ptr(evclass), _lib.ptr(n_procs),
+            _lib.ptr(target), e, ctypes.byref(rp), ctypes.byref(pp), _lib.ptr(stats), _lib.ptr(delays),
+            _lib.ptr(attrs), n_dump, k, int(bool(descending)), _lib.ptr(topk)))
+        return SweepResult(stats, delays=delays, topk=topk, attrs=attrs)
+
+    def decide_procset_events(self, events, ctx=None, host=False):
+        """(delays int64[n], [attrs _lib.PROC_ATTR_DTYPE[n_procs] per event], procs) of a batch of ProcSetEvents
+        under self.Seed: nmz_procset_decide on the GPU, or nmz_procset_decide_host on this thread."""
+        h, c, n_procs, _, procs = self.procset_inputs(events)
+        n, total = len(events), int(n_procs.sum())
+        delays = np.zeros(max(n, 1), np.int64)
+        attrs = np.zeros(max(total, 1), _lib.PROC_ATTR_DTYPE)
+        rp, pp = self._cached_params(), self.procset_params()
+        L = _lib.load()
+        if host:
+            _lib.check(L.nmz_procset_decide_host(int(self.Seed), _lib.ptr(h), _lib.ptr(c), _lib.ptr(n_procs), n,
+                                                 ctypes.byref(rp), ctypes.byref(pp), _lib.ptr(delays),
+                                                 _lib.ptr(attrs)))
+        else:
+            _lib.check(L.nmz_procset_decide((ctx or self._ctx()).handle, int(self.Seed), _lib.ptr(h), _lib.ptr(c),
+                                            _lib.ptr(n_procs), n, ctypes.byref(rp), ctypes.byref(pp),
+                                            _lib.ptr(delays), _lib.ptr(attrs)))
+        off = np.concatenate([[0], np.cumsum(n_procs, dtype=np.int64)])
+        return delays[:n], [attrs[off[i]:off[i + 1]] for i in range(n)], procs
+
+    def procset_action(self, event, procs, attrs):
+        """signal.NewProcSetSchedAction for one decided event: attrs[i] is slot i's nmz_proc_attr. A
+        SCHED_DEADLINE slot (dirichlet.go:70-79) gets Deadline = Period = 1 ms and Runtime = int(1e6 * ratio_i *
+        1.0 * numCPU), the ratios from Generator.dirichlet (outside the determinism contract, see the class)."""
+        ratios = None
+        pairs = []
+        for i, (pid, a) in enumerate(zip(procs, attrs)):
+            if int(a["policy"]) == SCHED_DEADLINE:
+                if ratios is None:
+                    if getattr(self, "_drng_seed", None) != self.Seed:
+                        self._drng, self._drng_seed = np.random.default_rng(self.Seed), self.Seed
+                    ratios = self._drng.dirichlet(np.ones(len(procs)))
+                base = 1_000_000
+                pairs.append((pid, sched_attr(a["policy"], a["flags"], runtime=int(base * ratios[i] * 1.0 *
+                                                                                   float(os.cpu_count() or 1)),
+                                              deadline=base, period=base)))
+            else:
+                pairs.append((pid, sched_attr(a["policy"], a["flags"], a["nice"], a["priority"])))
+        return ProcSetSchedAction(event, pairs)
+
+    @staticmethod
+    def _is_procset(ev):
+        cls = getattr(ev, "Class", None)
+        return cls is not None and cls() == PROCSET_CLASS
 
     def event_inputs(self, events, ctx=None):
         """events -> (evhash uint64[E], evclass uint8[E]) as the kernel consumes them. The event hashes of a
@@ -573,8 +702,8 @@ class Random(ExplorePolicy):
             _lib.check(_lib.load().nmz_fnv1a64_batch((ctx or self._ctx()).handle, _lib.ptr(off64), _lib.ptr(data),
                                                      len(events), _lib.ptr(evhash)))
         for i, ev in enumerate(events):
-            if ev.Class() == "ProcSetEvent":
-                raise ValueError("ProcSetEvent decisions belong to procPolicy (out of scope)")
+            if ev.Class() == PROCSET_CLASS:
+                raise ValueError("ProcSetEvent decisions belong to procPolicy: procset_inputs / ProcSetSweep")
             c = 0
             if ev.EntityID() in self.PrioritizedEntities:
                 c |= _lib.NMZ_EV_PRIORITIZED
@@ -601,8 +730,17 @@ class Random(ExplorePolicy):
         return SweepResult(stats, delays=delays, faults=faults, topk=topk)
 
     def decide_events(self, events, ctx=None):
-        """(delays int64[n], faults bool[n]) of a batch of events under self.Seed (nmz_random_decide)."""
+        """(delays int64[n], faults bool[n]) of a batch of events under self.Seed (nmz_random_decide). A
+        ProcSetEvent in the batch is decided by nmz_procset_decide (its delay; never a fault) and keeps its place."""
         ctx = ctx or self._ctx()
+        ps = [i for i, ev in enumerate(events) if self._is_procset(ev)]
+        if ps:
+            rest = [i for i in range(len(events)) if i not in set(ps)]
+            delays, faults = np.zeros(len(events), np.int64), np.zeros(len(events), bool)
+            delays[ps] = self.decide_procset_events([events[i] for i in ps], ctx=ctx)[0]
+            if rest:
+                delays[rest], faults[rest] = self.decide_events([events[i] for i in rest], ctx=ctx)
+            return delays, faults
         h, c = self.event_inputs(events)
         n = len(events)
         delays = np.zeros(max(n, 1), np.int64)
@@ -631,19 +769,32 @@ class Random(ExplorePolicy):
         return self._params
 
     def _decide_batch(self, events):
-        d, f = self.decide_events(events)
-        return [(int(dl), e.DefaultFaultAction() if fl else e.DefaultAction(), self.is_fixed(e))
-                for dl, fl, e in zip(d.tolist(), f.tolist(), events)]
+        out = [None] * len(events)
+        ps = [i for i, ev in enumerate(events) if self._is_procset(ev)]
+        if ps:  # procPolicy.Action (randompolicy.go:300-304); a mixed batch keeps its order
+            d, attrs, procs = self.decide_procset_events([events[i] for i in ps])
+            for j, i in enumerate(ps):
+                out[i] = (int(d[j]), self.procset_action(events[i], procs[j], attrs[j]), self.is_fixed(events[i]))
+        rest = [i for i in range(len(events)) if out[i] is None]
+        if rest:
+            d, f = self.decide_events([events[i] for i in rest])
+            for i, dl, fl in zip(rest, d.tolist(), f.tolist()):
+                e = events[i]
+                out[i] = (int(dl), e.DefaultFaultAction() if fl else e.DefaultAction(), self.is_fixed(e))
+        return out
 
     def event_class(self, ev):
-        if ev.Class() == "ProcSetEvent":
-            raise ValueError("ProcSetEvent decisions belong to procPolicy (out of scope)")
+        if ev.Class() == PROCSET_CLASS:
+            raise ValueError("ProcSetEvent decisions belong to procPolicy: procset_inputs / ProcSetSweep")
         c = _lib.NMZ_EV_PRIORITIZED if ev.EntityID() in self.PrioritizedEntities else 0
         return c | (_lib.NMZ_EV_FAULTABLE if ev.faultable() else 0)
 
     def _decide_one(self, event):
         """makeActionForEvent + the queue's delay draw on this thread (nmz_random_decide_host): the event's hash
         (FNV-1a 64 of its canonical JSON, nmz_fnv1a64_batch_host), its class, and the kernels' closed forms."""
+        if self._is_procset(event):  # procPolicy.Action on this thread (nmz_procset_decide_host)
+            d, attrs, procs = self.decide_procset_events([event], host=True)
+            return int(d[0]), self.procset_action(event, procs[0], attrs[0]), self.is_fixed(event)
         L = _lib.load()
         js = event.canonical_json()
         js = js.encode() if isinstance(js, str) else bytes(js)

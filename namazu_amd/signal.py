@@ -6,6 +6,8 @@ Only what the batch/online decision path consumes is modelled:
   * DefaultAction() / DefaultFaultAction() class   event.go:61-71,
     event_packet.go:45-47, event_filesystem.go:58-60, action_fault_*.go
   * Equals()              signal/signal.go:174-186 (uuid ignored)
+  * NewProcSetEvent / NewProcSetSchedAction   event_procset.go:26-42,
+    action_sched_procset.go:28-41
 
 Event hash (build-defined): evhash = FNV1a64 of the canonical JSON
 of the event map without "uuid", canonicalised the way Go's encoding/json
@@ -25,7 +27,9 @@ FNV_PRIME = 0x100000001B3
 _M64 = (1 << 64) - 1
 
 FAULTABLE_CLASSES = {"PacketEvent": "PacketFaultAction", "FilesystemEvent": "FilesystemFaultAction"}
-OUT_OF_SCOPE_CLASSES = {"ProcSetEvent"}  # random policy routes these to procPolicy (host side)
+PROCSET_CLASS = "ProcSetEvent"  # the random policy routes these to its procPolicy (randompolicy.go:300-304)
+# linuxsched policy numbers and flag of a ProcSetSchedAction's attributes
+SCHED_NORMAL, SCHED_RR, SCHED_BATCH, SCHED_DEADLINE, SCHED_RESET_ON_FORK = 0, 2, 3, 6, 1
 
 
 def fnv1a64(data: bytes, h: int = FNV_OFFSET) -> int:
@@ -133,6 +137,22 @@ class Action:
         return self.m
 
 
+def sched_attr(policy=SCHED_NORMAL, flags=0, nice=0, priority=0, runtime=0, deadline=0, period=0):
+    """linuxsched.SchedAttr as encoding/json marshals it: the exported field names, durations as integer ns."""
+    return {"Policy": int(policy), "Flags": int(flags), "Nice": int(nice), "Priority": int(priority),
+            "Runtime": int(runtime), "Deadline": int(deadline), "Period": int(period)}
+
+
+class ProcSetSchedAction(Action):
+    """signal.NewProcSetSchedAction (action_sched_procset.go:28-41): the event's entity, a top-level "event_uuid",
+    and option {"attrs": {pid string: SchedAttr}}. attrs: (pid, attr) pairs in slot order or a dict; with a
+    duplicated pid the later slot wins, as in the reference's map."""
+
+    def __init__(self, event, attrs):
+        pairs = attrs.items() if isinstance(attrs, dict) else attrs
+        super().__init__("ProcSetSchedAction", event.EntityID(), event, option={"attrs": dict(pairs)})
+
+
 class Event:
     """Map-based event (BasicEvent); construct from a JSON map or string."""
 
@@ -156,6 +176,14 @@ class Event:
         if replay_hint is not None:
             m["replay_hint"] = replay_hint
         return cls(m)
+
+    @classmethod
+    def procset(cls, entity, procs, option=None):
+        """signal.NewProcSetEvent (event_procset.go:26-42): deferred=false, option {"procs": [...]} plus `option`."""
+        opt = {"procs": list(procs)}
+        opt.update(option or {})
+        return cls({"uuid": str(_uuid.uuid4()), "entity": entity, "type": "event", "class": PROCSET_CLASS,
+                    "deferred": False, "option": opt})
 
     def ID(self):
         return self.m.get("uuid", "")

@@ -81,6 +81,49 @@ static void null_ctx_cases() {
     CHECK(std::strlen(nmz_last_error()) > 0);
 }
 
+// ProcSetEvent decisions on the host at the limits (512 processes, prioritized 256: the marked-slot set and the
+// attribute rows are written to their last element) and their argument checks
+static void procset_cases() {
+    nmz_random_params rp;
+    nmz_procset_params pp;
+    CHECK(nmz_random_params_resolve(30000000, 100000000, 0.1, &rp) == NMZ_OK);
+    CHECK(nmz_procset_params_resolve(nullptr, 1, 3, 0.1, &pp) == NMZ_OK && pp.policy == NMZ_PROC_MILD);
+    CHECK(nmz_procset_params_resolve("", 0, 3, 0.1, &pp) == NMZ_OK && pp.policy == NMZ_PROC_MILD && !pp.use_batch);
+    CHECK(nmz_procset_params_resolve("nope", 1, 3, 0.1, &pp) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "bad procPolicy nope") != nullptr);
+    CHECK(nmz_procset_params_resolve("dirichlet", 1, 3, 1.5, &pp) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "bad procPolicyParam.resetProbability 1.500000") != nullptr);
+    CHECK(nmz_procset_params_resolve("dirichlet", 1, 3, std::nan(""), &pp) == NMZ_EINVAL);
+    CHECK(nmz_procset_params_resolve("extreme", 1, 257, 0.1, &pp) == NMZ_EINVAL);
+    CHECK(nmz_procset_params_resolve("mild", 1, 3, 0.1, nullptr) == NMZ_EINVAL);
+    const uint64_t eh[4] = {1, 0x9E3779B97F4A7C15ull, ~0ull, 12345};
+    const uint8_t ec[4] = {0, 1, 0, 1};
+    uint32_t n[4] = {512, 1, 410, 512};
+    std::vector<nmz_proc_attr> at(512 + 1 + 410 + 512);
+    int64_t d[4];
+    const char *names[3] = {"mild", "extreme", "dirichlet"};
+    for (const char *name : names) {
+        CHECK(nmz_procset_params_resolve(name, 1, 256, 0.999, &pp) == NMZ_OK);
+        for (uint64_t seed = 0; seed < 50; ++seed)
+            CHECK(nmz_procset_decide_host(seed, eh, ec, n, 4, &rp, &pp, d, at.data()) == NMZ_OK);
+        CHECK(d[0] >= 30000000 && d[0] < 100000000 && d[1] >= 24000000 && d[1] < 80000000);
+    }
+    CHECK(nmz_procset_decide_host(1, eh, ec, n, 0, &rp, &pp, nullptr, nullptr) == NMZ_OK);
+    n[1] = 0;  // dirichlet: an event without a process
+    CHECK(nmz_procset_decide_host(1, eh, ec, n, 4, &rp, &pp, d, at.data()) == NMZ_EINVAL);
+    n[1] = 513;
+    CHECK(nmz_procset_decide_host(1, eh, ec, n, 4, &rp, &pp, d, at.data()) == NMZ_EINVAL);
+    n[1] = 1;
+    const uint8_t bad[4] = {0, NMZ_EV_FAULTABLE, 0, 0};
+    CHECK(nmz_procset_decide_host(1, eh, bad, n, 4, &rp, &pp, d, at.data()) == NMZ_EINVAL);
+    CHECK(nmz_procset_decide_host(1, eh, ec, n, 4, &rp, nullptr, d, at.data()) == NMZ_EINVAL);
+    CHECK(nmz_procset_decide_host(1, eh, ec, n, 4, nullptr, &pp, d, at.data()) == NMZ_EINVAL);
+    CHECK(nmz_procset_decide_host(1, nullptr, ec, n, 4, &rp, &pp, d, at.data()) == NMZ_EINVAL);
+    CHECK(nmz_procset_decide(nullptr, 1, eh, ec, n, 4, &rp, &pp, d, at.data()) == NMZ_EINVAL);
+    CHECK(nmz_procset_sweep(nullptr, 0, 1, eh, ec, n, nullptr, 4, &rp, &pp, nullptr, nullptr, nullptr, 0, 0, 1,
+                            nullptr) == NMZ_EINVAL);
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -127,6 +170,7 @@ static void thread_local_errors(int n_threads, int iters) {
 int main() {
     params_cases();
     null_ctx_cases();
+    procset_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
