@@ -14,6 +14,9 @@
  *                             explorepolicy/replayable/replayablepolicy.go:100-126
  *                             (FNV-1a64(seed || hint) % maxInterval), batched over
  *                             seeds x events.
+ *   nmz_replayable_order_* -> the release times Replayable.QueueEvent gives,
+ *                             replayablepolicy.go:100-126 (arrival + interval), checked
+ *                             against event-order constraints per seed and batched over seeds.
  *   nmz_random_sweep*      -> Random.QueueEvent + makeActionForEvent
  *                             explorepolicy/random/randompolicy.go:300-316,332-346
  *                             + util/queue/impl.go:35-46,94-128 (Int63n delay,
@@ -114,7 +117,7 @@ int nmz_device_count(int *count);
 int nmz_ctx_stream(nmz_ctx *ctx, void **stream);
 
 /* Kernel timing (HIP events recorded on the launch stream around the dominant
- * kernels: "replayable_sweep", "random_sweep", "procset_sweep", "ed_tile"). on = 0 off, 1 events and
+ * kernels: "replayable_sweep", "random_sweep", "procset_sweep", "order_sweep", "ed_tile"). on = 0 off, 1 events and
  * spans, NMZ_TIMING_SPANS (2) the kernels' own spans only (no event records between a
  * stream's launches: each record is a marker the queue waits on, ~6 us). */
 #define NMZ_TIMING_SPANS 2
@@ -268,6 +271,81 @@ int nmz_replayable_sweep_decimal_topk_dev(nmz_replayable_plan *plan, uint64_t se
  * since the last call, one thread per event. Synchronous; scratch is owned by the context. */
 int nmz_replayable_decide(nmz_ctx *ctx, const uint8_t *seed, uint32_t seed_len, const uint32_t *hint_off,
                           const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns, int64_t *delays);
+
+/* ---- replayable policy: seeds against event-order constraints ----------------
+ * Replayable.QueueEvent releases every event at arrival + determineInterval(event)
+ * (replayablepolicy.go:100-126), so a seed is a delivery order. For one trace the caller gives the hints
+ * (CSR, n_events, as above), arrival_ns[n_events] (int64, when each event reached QueueEvent, any origin) and
+ * n_constraints constraints {before, after, margin_ns}. For seed s:
+ *     release[s][e] = arrival_ns[e] + delay[s][e]      (delay as nmz_replayable_sweep; 0 when max_interval_ns == 0)
+ *     slack[s][c]   = release[s][after_c] - release[s][before_c] - margin_c
+ * Constraint c is satisfied iff slack >= 0: event `before` is delivered at least margin_ns ahead of `after`
+ * (margin_ns >= 1 makes the order strict; use a margin of timer-jitter size, the reference sleeps in real time).
+ * Limits, each NMZ_EINVAL with a message: 1 <= n_constraints <= 64; before != after, both < n_events;
+ * 0 <= arrival_ns <= 2^61; 1 <= margin_ns <= 2^61; 0 <= max_interval_ns <= 2^61 (every slack then fits int64 and
+ * INT64_MIN stays free as the top-k sentinel). Two events with equal hints are legal: their slack is the same for
+ * every seed.
+ * Seeds are ranked by (n_satisfied desc, min_slack_ns desc, seed asc): among seeds satisfying everything, the one
+ * whose tightest constraint has the most room. That is nmz_topk_entry's order, and the sweeps write their top-k as
+ * nmz_topk_entry with
+ *     n_fault = n_satisfied, sum_delay_ns = min_slack_ns, first_fault = argmin_constraint,
+ *     seed = the CSR index (+ seed0) or the decimal value, as the sweeps above,
+ * and the same sentinel {UINT64_MAX, INT64_MIN, 0, NMZ_NONE} past n_seeds, so nmz_topk_merge_dev merges the lists of
+ * several sweeps and namazu_amd/replay.py turns them into NMZ_REPLAY_SEED unchanged. */
+typedef struct nmz_order_constraint {
+    uint32_t before;   /* event that must be released first      */
+    uint32_t after;    /* event that must be released later      */
+    int64_t margin_ns; /* by at least this much                  */
+} nmz_order_constraint;
+
+/* Per-seed statistics of an order sweep, 24 bytes. */
+typedef struct nmz_order_stats {
+    uint64_t sat_mask;          /* bit c set <=> constraint c is satisfied          */
+    int64_t min_slack_ns;       /* minimum slack over the constraints               */
+    uint32_t n_satisfied;       /* popcount(sat_mask)                               */
+    uint32_t argmin_constraint; /* the first constraint attaining min_slack_ns      */
+} nmz_order_stats;
+
+/* One seed on the calling host thread, no device work (replayablepolicy.go:100-126): the statistics (may be NULL)
+ * and, if slack != NULL, slack[n_constraints]. Vets a candidate seed before a replay. */
+int nmz_replayable_order_host(const uint8_t *seed, uint32_t seed_len, const uint32_t *hint_off,
+                              const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns,
+                              const int64_t *arrival_ns, const nmz_order_constraint *constraints,
+                              uint32_t n_constraints, nmz_order_stats *stats, int64_t *slack);
+/* The plan holds the per-constraint device tables of one trace and the scratch of one sweep of up to max_seeds
+ * (< 2^32) seeds; host arrays are borrowed for the call. Like the other plans it serves one stream at a time (two
+ * streams take one plan each). Destroy waits for the plan's sweeps. Same reference lines
+ * (replayablepolicy.go:100-126). */
+typedef struct nmz_replayable_order_plan nmz_replayable_order_plan;
+int nmz_replayable_order_plan_create(nmz_ctx *ctx, const uint32_t *hint_off, const uint8_t *hint_bytes,
+                                     uint32_t n_events, int64_t max_interval_ns, const int64_t *arrival_ns,
+                                     const nmz_order_constraint *constraints, uint32_t n_constraints,
+                                     uint64_t max_seeds, nmz_replayable_order_plan **out);
+int nmz_replayable_order_plan_destroy(nmz_replayable_order_plan *plan);
+/* The seeds "seed_lo" .. "seed_lo + n_seeds - 1" (decimal strings generated on the device, wrapping past 2^64 as
+ * nmz_replayable_sweep_decimal_topk_dev; replayablepolicy.go:74-87 seed string, :100-126 release times), enqueued on
+ * `stream` (NULL = the context's). d_stats[n_seeds] may be NULL: the sweep then writes only d_topk[k] (k <= 256;
+ * k == 0: no top-k), the hot form. Top-k .seed = the seed's integer value. */
+int nmz_replayable_order_sweep_decimal_dev(nmz_replayable_order_plan *plan, uint64_t seed_lo, uint64_t n_seeds,
+                                           uint32_t k, nmz_order_stats *d_stats /* may be NULL */,
+                                           nmz_topk_entry *d_topk, void *stream);
+/* The same for arbitrary seed strings (device CSR d_seed_off[n_seeds + 1] into d_seed_bytes; the empty seed is the
+ * reference's default, replayablepolicy.go:74-81). Top-k .seed = seed0 + the seed's index. */
+int nmz_replayable_order_sweep_dev(nmz_replayable_order_plan *plan, const uint32_t *d_seed_off,
+                                   const uint8_t *d_seed_bytes, uint64_t n_seeds, uint64_t seed0, uint32_t k,
+                                   nmz_order_stats *d_stats /* may be NULL */, nmz_topk_entry *d_topk, void *stream);
+/* Host pointers, synchronous, built on the plan (replayablepolicy.go:100-126): stats[n_seeds] and topk[k] may each
+ * be NULL; k <= 256. Top-k .seed = the seed's index in the CSR, or its integer value for the decimal form. */
+int nmz_replayable_order_sweep(nmz_ctx *ctx, const uint32_t *seed_off, const uint8_t *seed_bytes, uint64_t n_seeds,
+                               const uint32_t *hint_off, const uint8_t *hint_bytes, uint32_t n_events,
+                               int64_t max_interval_ns, const int64_t *arrival_ns,
+                               const nmz_order_constraint *constraints, uint32_t n_constraints, uint32_t k,
+                               nmz_order_stats *stats, nmz_topk_entry *topk);
+int nmz_replayable_order_sweep_decimal(nmz_ctx *ctx, uint64_t seed_lo, uint64_t n_seeds, const uint32_t *hint_off,
+                                       const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns,
+                                       const int64_t *arrival_ns, const nmz_order_constraint *constraints,
+                                       uint32_t n_constraints, uint32_t k, nmz_order_stats *stats,
+                                       nmz_topk_entry *topk);
 
 /* ---- random policy sweep ------------------------------------------------
  * Seeds are the integers seed0 .. seed0+n_seeds-1. For seed s and event e

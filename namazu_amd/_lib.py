@@ -46,6 +46,12 @@ PROCSET_STATS_DTYPE = np.dtype([("sum_delay_ns", "<u8"), ("score_sum", "<i8"), (
 assert PROCSET_STATS_DTYPE.itemsize == 32
 PROCSET_TOPK_DTYPE = np.dtype([("seed", "<u8"), ("target_score", "<i8")])
 assert PROCSET_TOPK_DTYPE.itemsize == 16
+# event-order constraints of the replayable policy (nmz_order_constraint, nmz_order_stats)
+ORDER_CONSTRAINT_DTYPE = np.dtype([("before", "<u4"), ("after", "<u4"), ("margin_ns", "<i8")])
+assert ORDER_CONSTRAINT_DTYPE.itemsize == 16
+ORDER_STATS_DTYPE = np.dtype([("sat_mask", "<u8"), ("min_slack_ns", "<i8"), ("n_satisfied", "<u4"),
+                              ("argmin_constraint", "<u4")])
+assert ORDER_STATS_DTYPE.itemsize == 24
 
 
 class NmzLibraryError(RuntimeError):
@@ -96,6 +102,13 @@ SIGNATURES = {
     "nmz_replayable_plan_kernel": (_int, [_P]),
     "nmz_replayable_sweep_dev": (_int, [_P, _P, _P, _u64, _P, _P]),
     "nmz_replayable_sweep_topk_dev": (_int, [_P, _P, _P, _u64, _u64, _u32, _P, _P, _P]),
+    "nmz_replayable_order_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _u32, _P, _P]),
+    "nmz_replayable_order_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _u32, _u64, ctypes.POINTER(_P)]),
+    "nmz_replayable_order_plan_destroy": (_int, [_P]),
+    "nmz_replayable_order_sweep_decimal_dev": (_int, [_P, _u64, _u64, _u32, _P, _P, _P]),
+    "nmz_replayable_order_sweep_dev": (_int, [_P, _P, _P, _u64, _u64, _u32, _P, _P, _P]),
+    "nmz_replayable_order_sweep": (_int, [_P, _P, _P, _u64, _P, _P, _u32, _i64, _P, _P, _u32, _u32, _P, _P]),
+    "nmz_replayable_order_sweep_decimal": (_int, [_P, _u64, _u64, _P, _P, _u32, _i64, _P, _P, _u32, _u32, _P, _P]),
     "nmz_replayable_decide": (_int, [_P, _P, _u32, _P, _P, _u32, _i64, _P]),
     "nmz_random_decide": (_int, [_P, _u64, _P, _P, _u32, _P, _P, _P]),
     "nmz_random_sweep": (_int, [_P, _u64, _u64, _P, _P, _u32, _P, _P, _P, _P, _u64, _u32, _P]),

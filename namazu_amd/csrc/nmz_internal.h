@@ -10,6 +10,12 @@ int topk_merge_lists(hipStream_t st, nmz_topk_entry *a, nmz_topk_entry *b, uint6
 int topk_select(hipStream_t st, const nmz_sched_stats *d_stats, uint64_t n, uint64_t seed0, uint32_t k,
                 nmz_topk_entry *d_scratch, nmz_topk_entry *d_out);
 
+// replayable.hip's seed prefix kernels for another unit (order.hip): h0[S] = FNV-1a 64 of each seed string of the
+// device CSR, or (d_soff == nullptr) of the decimal strings of dec_lo .. dec_lo + S - 1 (wrapping past 2^64);
+// rows[bucket_hist_u32(S)] receives the kernels' bucket counts
+int seed_prefix_launch(hipStream_t st, const uint32_t *d_soff, const uint8_t *d_sbytes, uint64_t dec_lo, uint64_t S,
+                       uint64_t *h0, uint32_t *rows);
+
 // scratch carving helper: bump allocator over one device buffer (256-B aligned)
 struct Carve {
     char *base;

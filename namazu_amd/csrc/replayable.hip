@@ -1950,6 +1950,21 @@ static void seeds_destroy_locked(nmz_replayable_seeds *seeds) {
     delete seeds;
 }
 
+// the seeds' prefix hashes for another unit's sweep (order.hip): k_seed_prefix over the CSR, or (d_soff == nullptr)
+// k_seed_prefix_decimal over dec_lo .. dec_lo + S - 1; rows receives the kernels' bucket counts
+int seed_prefix_launch(hipStream_t st, const uint32_t *d_soff, const uint8_t *d_sbytes, uint64_t dec_lo, uint64_t S,
+                       uint64_t *h0, uint32_t *rows) {
+    if (S == 0) return NMZ_OK;
+    if (d_soff)
+        hipLaunchKernelGGL(k_seed_prefix, dim3(ceil_div(S, BUCKET_BLK)), dim3(256), 0, st, d_soff, d_sbytes, S, h0,
+                           rows);
+    else
+        hipLaunchKernelGGL(k_seed_prefix_decimal, dim3(ceil_div(S, BUCKET_BLK)), dim3(256), 0, st, dec_lo, S, h0,
+                           rows);
+    NMZ_HIP(hipGetLastError());
+    return NMZ_OK;
+}
+
 }  // namespace nmz
 
 using namespace nmz;

@@ -63,6 +63,10 @@ struct TopkShared {
 // A 64-bit coarse key (monotone in the order, not strict) gives a threshold tau = the k-th largest
 // per-thread maximum: at least k entries reach it, and every member of the chunk's top-k does. The
 // survivors (typically ~k) are ranked exactly by counting and written to their slot.
+// CARRY: the many-ties rounds carry a thread's best entry by value instead of indexing e[] with a runtime index,
+// which moves the caller's register arrays into scratch memory (k_topk_chunk, 208 bytes per lane); a sweep kernel
+// that fuses the selection (order.hip) takes CARRY = true and keeps its state in registers. Same results.
+template <bool CARRY = false>
 __device__ inline void topk_block_select(const nmz_topk_entry (&e)[TOPK_PER_THREAD], uint32_t k,
                                          nmz_topk_entry *__restrict__ o, TopkShared &sh) {
     const uint32_t t = threadIdx.x;
@@ -118,12 +122,24 @@ __device__ inline void topk_block_select(const nmz_topk_entry (&e)[TOPK_PER_THRE
     uint32_t used = 0;
     for (uint32_t i = 0; i < k && i < c; ++i) {
         int br = -1;
+        if constexpr (CARRY) {
+            nmz_topk_entry bx = topk_sentinel();
 #pragma unroll
-        for (uint32_t r = 0; r < TOPK_PER_THREAD; ++r)
-            if (!((used >> r) & 1u) && ck[r] >= tau && !topk_is_sentinel(e[r]) &&
-                (br < 0 || topk_before(e[r], r * TOPK_THREADS + t, e[br], (uint32_t)br * TOPK_THREADS + t)))
-                br = (int)r;
-        sh.cand[t] = br >= 0 ? e[br] : topk_sentinel();
+            for (uint32_t r = 0; r < TOPK_PER_THREAD; ++r)
+                if (!((used >> r) & 1u) && ck[r] >= tau && !topk_is_sentinel(e[r]) &&
+                    (br < 0 || topk_before(e[r], r * TOPK_THREADS + t, bx, (uint32_t)br * TOPK_THREADS + t))) {
+                    br = (int)r;
+                    bx = e[r];
+                }
+            sh.cand[t] = bx;
+        } else {
+#pragma unroll
+            for (uint32_t r = 0; r < TOPK_PER_THREAD; ++r)
+                if (!((used >> r) & 1u) && ck[r] >= tau && !topk_is_sentinel(e[r]) &&
+                    (br < 0 || topk_before(e[r], r * TOPK_THREADS + t, e[br], (uint32_t)br * TOPK_THREADS + t)))
+                    br = (int)r;
+            sh.cand[t] = br >= 0 ? e[br] : topk_sentinel();
+        }
         sh.cidx[t] = br >= 0 ? (uint32_t)br * TOPK_THREADS + t : UINT32_MAX;
         __syncthreads();
         for (uint32_t st = TOPK_THREADS / 2; st; st >>= 1) {

@@ -466,6 +466,79 @@ class Replayable(ExplorePolicy):
             int(self.MaxInterval), _lib.ptr(stats), _lib.ptr(delays), n_dump, k, _lib.ptr(topk)))
         return SweepResult(stats, delays=delays, topk=topk)
 
+    @staticmethod
+    def order_constraints(constraints):
+        """(before, after, margin_ns) tuples -> ORDER_CONSTRAINT_DTYPE array (an array of that dtype passes through):
+        event `before` must be released at least margin_ns ahead of event `after`. The library checks the limits."""
+        if isinstance(constraints, np.ndarray) and constraints.dtype == _lib.ORDER_CONSTRAINT_DTYPE:
+            return np.ascontiguousarray(constraints)
+        out = np.zeros(len(constraints), _lib.ORDER_CONSTRAINT_DTYPE)
+        for i, c in enumerate(constraints):
+            if len(c) != 3:
+                raise ValueError(f"constraint {i}: expected (before, after, margin_ns), got {c!r}")
+            b, a, m = (int(x) for x in c)
+            if not (0 <= b < 2**32 and 0 <= a < 2**32 and -2**63 <= m < 2**63):
+                raise ValueError(f"constraint {i}: {c!r} does not fit (uint32, uint32, int64)")
+            out[i] = (b, a, m)
+        return out
+
+    def OrderSweep(self, hints, arrival_ns, constraints, seeds=None, seed_lo=None, n_seeds=None, k=0,
+                   want_stats=True, ctx=None):
+        """Rank seeds by the delivery order they produce (nmz_replayable_order_sweep[_decimal]).
+
+        QueueEvent releases event e at arrival_ns[e] + determineInterval(e) (replayablepolicy.go:100-126), so a
+        seed is a delivery order. constraints are (before, after, margin_ns) tuples: satisfied iff
+        release[after] - release[before] - margin_ns >= 0. Seeds are either `seeds` (a list of strings; top-k seed =
+        index) or the decimal strings of seed_lo .. seed_lo + n_seeds - 1 (top-k seed = the integer). Returns a
+        SweepResult: stats[n_seeds] (ORDER_STATS_DTYPE; None unless want_stats) and topk[k] (TOPK_DTYPE with
+        n_fault = n_satisfied, sum_delay_ns = min_slack_ns, first_fault = argmin_constraint), best first by
+        (n_satisfied desc, min_slack desc, seed asc). From the top-k to a replay of the reference:
+
+            hints = [e.ReplayHint() for e in trace]          # "event 12 before event 7, by 1 ms at least"
+            r = policy.OrderSweep(hints, arrival_ns, [(12, 7, 1_000_000)], seeds=seeds, k=8, want_stats=False)
+            best = replay.replayable_seeds(r.topk, seeds)    # seed strings, best first
+            env = replay.replay_env(best[0], os.environ)     # NMZ_REPLAY_SEED for `nmz run`
+        """
+        ctx = ctx or self._ctx()
+        hoff, hb = to_csr(hints)
+        arr = np.ascontiguousarray(arrival_ns, np.int64)
+        if len(arr) != len(hints):
+            raise ValueError(f"{len(arr)} arrival times for {len(hints)} hints")
+        cons = self.order_constraints(constraints)
+        if (seeds is None) == (seed_lo is None):
+            raise ValueError("give either seeds or seed_lo and n_seeds")
+        n = len(seeds) if seeds is not None else int(n_seeds)
+        stats = np.zeros(n, _lib.ORDER_STATS_DTYPE) if want_stats else None
+        topk = np.zeros(k, _lib.TOPK_DTYPE) if k else None
+        L = _lib.load()
+        if seeds is not None:
+            soff, sb = to_csr(seeds)
+            _lib.check(L.nmz_replayable_order_sweep(
+                ctx.handle, _lib.ptr(soff), _lib.ptr(sb), n, _lib.ptr(hoff), _lib.ptr(hb), len(hints),
+                int(self.MaxInterval), _lib.ptr(arr), _lib.ptr(cons), len(cons), k, _lib.ptr(stats), _lib.ptr(topk)))
+        else:
+            _lib.check(L.nmz_replayable_order_sweep_decimal(
+                ctx.handle, int(seed_lo) & (2**64 - 1), n, _lib.ptr(hoff), _lib.ptr(hb), len(hints),
+                int(self.MaxInterval), _lib.ptr(arr), _lib.ptr(cons), len(cons), k, _lib.ptr(stats), _lib.ptr(topk)))
+        return SweepResult(stats, topk=topk)
+
+    def order_slack(self, event_hints, arrival_ns, constraints):
+        """The host check of self.Seed (nmz_replayable_order_host, no GPU): (stats, slack) with stats one
+        ORDER_STATS_DTYPE record and slack[len(constraints)] int64 ns. Vets a candidate seed before a replay."""
+        hoff, hb = to_csr(event_hints)
+        arr = np.ascontiguousarray(arrival_ns, np.int64)
+        if len(arr) != len(event_hints):
+            raise ValueError(f"{len(arr)} arrival times for {len(event_hints)} hints")
+        cons = self.order_constraints(constraints)
+        seed = self.Seed.encode() if isinstance(self.Seed, str) else bytes(self.Seed)
+        sb = np.frombuffer(seed, np.uint8).copy() if seed else np.zeros(1, np.uint8)
+        stats = np.zeros(1, _lib.ORDER_STATS_DTYPE)
+        slack = np.zeros(max(len(cons), 1), np.int64)
+        _lib.check(_lib.load().nmz_replayable_order_host(
+            _lib.ptr(sb), len(seed), _lib.ptr(hoff), _lib.ptr(hb), len(event_hints), int(self.MaxInterval),
+            _lib.ptr(arr), _lib.ptr(cons), len(cons), _lib.ptr(stats), _lib.ptr(slack)))
+        return stats[0], slack[:len(cons)]
+
     def decide_intervals(self, events, ctx=None):
         """determineInterval for a batch of events under self.Seed (nmz_replayable_decide)."""
         ctx = ctx or self._ctx()

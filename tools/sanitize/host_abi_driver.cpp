@@ -124,6 +124,72 @@ static void procset_cases() {
                             nullptr) == NMZ_EINVAL);
 }
 
+// nmz_replayable_order_host (replayablepolicy.go:100-126): a known answer, every limit, optional outputs
+static void order_cases() {
+    std::vector<uint32_t> off(17, 0);
+    std::string bytes;
+    std::vector<int64_t> arrival(16);
+    for (int i = 0; i < 16; ++i) {
+        bytes += "hint-entity-" + std::to_string(i % 4) + "-" + std::to_string(i);
+        off[i + 1] = (uint32_t)bytes.size();
+        arrival[i] = (int64_t)i * 5000000;
+    }
+    const uint8_t *hb = reinterpret_cast<const uint8_t *>(bytes.data());
+    const nmz_order_constraint cons[5] = {{5, 0, 1000000}, {9, 2, 1000000}, {4, 3, 1}, {12, 7, 10000000}, {14, 1, 1}};
+    const uint8_t seed[4] = {'1', '0', '2', '9'};
+    nmz_order_stats st;
+    int64_t slack[64];
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 100000000, arrival.data(), cons, 5, &st, slack) ==
+          NMZ_OK);
+    CHECK(st.n_satisfied == 5 && st.sat_mask == 31 && st.min_slack_ns == 3735120 && st.argmin_constraint == 4);
+    CHECK(slack[4] == 3735120);
+    CHECK(nmz_replayable_order_host(nullptr, 0, off.data(), hb, 16, 0, arrival.data(), cons, 5, &st, nullptr) == NMZ_OK);
+    CHECK(st.n_satisfied == 0 && st.min_slack_ns == -65000001 && st.argmin_constraint == 4);
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, (int64_t)1 << 61, arrival.data(), cons, 5, nullptr,
+                                    nullptr) == NMZ_OK);
+    std::vector<nmz_order_constraint> many(65, cons[0]);
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), many.data(), 64, &st, slack) ==
+          NMZ_OK);
+    CHECK(st.sat_mask == 0 && st.argmin_constraint == 0 && slack[63] == -26000000);
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), many.data(), 65, &st, slack) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "n_constraints") != nullptr);
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), cons, 0, &st, slack) == NMZ_EINVAL);
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), nullptr, 1, &st, slack) ==
+          NMZ_EINVAL);
+    nmz_order_constraint bad = {3, 3, 1};
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), &bad, 1, &st, slack) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "before == after") != nullptr);
+    bad = {16, 3, 1};
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), &bad, 1, &st, slack) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "out of range") != nullptr);
+    bad = {1, 3, 0};
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), &bad, 1, &st, slack) == NMZ_EINVAL);
+    bad = {1, 3, ((int64_t)1 << 61) + 1};
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), &bad, 1, &st, slack) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "margin_ns") != nullptr);
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, -1, arrival.data(), cons, 5, &st, slack) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "max_interval_ns") != nullptr);
+    arrival[7] = -1;
+    CHECK(nmz_replayable_order_host(seed, 4, off.data(), hb, 16, 1, arrival.data(), cons, 5, &st, slack) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "arrival_ns[7]") != nullptr);
+    arrival[7] = 35000000;
+    CHECK(nmz_replayable_order_host(nullptr, 4, off.data(), hb, 16, 1, arrival.data(), cons, 5, &st, slack) ==
+          NMZ_EINVAL);
+    // the device entry points reject a NULL context or plan before any device work
+    nmz_replayable_order_plan *plan = nullptr;
+    nmz_topk_entry tk[2];
+    CHECK(nmz_replayable_order_plan_create(nullptr, off.data(), hb, 16, 1, arrival.data(), cons, 5, 10, &plan) ==
+          NMZ_EINVAL);
+    CHECK(nmz_replayable_order_plan_destroy(nullptr) == NMZ_OK);
+    CHECK(nmz_replayable_order_sweep_decimal_dev(nullptr, 0, 1, 1, nullptr, tk, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_replayable_order_sweep_dev(nullptr, nullptr, nullptr, 0, 0, 1, nullptr, tk, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_replayable_order_sweep(nullptr, off.data(), hb, 1, off.data(), hb, 16, 1, arrival.data(), cons, 5, 1,
+                                     nullptr, tk) == NMZ_EINVAL);
+    CHECK(nmz_replayable_order_sweep_decimal(nullptr, 0, 1, off.data(), hb, 16, 1, arrival.data(), cons, 5, 1, nullptr,
+                                             tk) == NMZ_EINVAL);
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -171,6 +237,7 @@ int main() {
     params_cases();
     null_ctx_cases();
     procset_cases();
+    order_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
