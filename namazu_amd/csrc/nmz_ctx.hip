@@ -363,8 +363,6 @@ int nmz_close(nmz_ctx *ctx) {
     }
     {
         CtxGuard g(ctx);
-        for (int i = 0; i < 2; ++i)
-            if (ctx->sweep_st[i]) (void)hipStreamDestroy(ctx->sweep_st[i]);
         for (int i = 0; i < 3; ++i)
             if (ctx->sweep_ev[i]) (void)hipEventDestroy(ctx->sweep_ev[i]);
         ctx->tkpin.release();

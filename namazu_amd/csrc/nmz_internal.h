@@ -10,12 +10,6 @@ int topk_merge_lists(hipStream_t st, nmz_topk_entry *a, nmz_topk_entry *b, uint6
 int topk_select(hipStream_t st, const nmz_sched_stats *d_stats, uint64_t n, uint64_t seed0, uint32_t k,
                 nmz_topk_entry *d_scratch, nmz_topk_entry *d_out);
 
-// replayable.hip's seed prefix kernels for another unit (order.hip): h0[S] = FNV-1a 64 of each seed string of the
-// device CSR, or (d_soff == nullptr) of the decimal strings of dec_lo .. dec_lo + S - 1 (wrapping past 2^64);
-// rows[bucket_hist_u32(S)] receives the kernels' bucket counts
-int seed_prefix_launch(hipStream_t st, const uint32_t *d_soff, const uint8_t *d_sbytes, uint64_t dec_lo, uint64_t S,
-                       uint64_t *h0, uint32_t *rows);
-
 // scratch carving helper: bump allocator over one device buffer (256-B aligned)
 struct Carve {
     char *base;
@@ -177,68 +171,5 @@ int ed_wide_launch(const EdWideArgs &A, uint32_t band, hipStream_t st);
 // stored traces of A; in-band results into A.knn + q * k
 int ed_wide_query_launch(const EdWideArgs &A, uint32_t band, const uint32_t *qpeq, uint64_t qstride,
                          const uint32_t *qlen, uint32_t n_q, hipStream_t st);
-
-// replayable plan: one hint-length class (a segment of every table row)
-struct ClassInfo {
-    uint64_t pn;     // P^len
-    uint32_t start;  // first position in the length-sorted event order
-    uint32_t count;
-};
-// K1 wavelet-tree statistics (replayable_wt.hip): per-row images built once per plan, staged into LDS per sweep
-struct WtState {
-    bool on = false;
-    uint32_t rb16 = 0, n_classes = 0, msh = 0;
-    uint32_t bb = 5;                        // rank blocks of 2^bb ranks below the tree's levels (replayable_wt.hip)
-    uint4 *d_blob = nullptr;                // [256][rb16] row images
-    unsigned long long *d_rowsum = nullptr;  // [256] sum of C mod m over the row
-    void *d_classes = nullptr;              // [n_classes] segment descriptors
-    DevBuf mem;                             // the row images
-    DevBuf aux;                             // separate path: row sums and segment descriptors
-};
-bool wt_enabled();
-struct WtClass {
-    uint64_t pn;              // P^len
-    uint32_t start, n;        // table segment (C order)
-    uint32_t o_lv, o_cm;      // byte offsets in the row image: wavelet levels [K][nw] {bits, ones before};
-    uint32_t o_chi, o_e;      //   Cm by rank (+ sentinel); C's high word by position (+ sentinel); e by rank (u16)
-    uint32_t o_im, o_ic;      //   bucket indexes (u16): first rank with Cm >= b << msh (257); first position
-                              //   with C_hi >= b << 24 (256)
-    uint32_t K, nw;           // rank bits (2^K > n); words per level (n / 32 + 1)
-    uint32_t rS;              // lifting-search rounds (the largest bucket's bit length; set by the plan kernel)
-    uint32_t o_mk;            //   block masks [(n >> bb) + 1][2^bb + 1] of 2^bb bits: the ranks (bit r mod 2^bb)
-                              //   among the first o entries of each 2^bb-rank block's node, o = 0..2^bb
-    uint32_t order;           // plan kernel: the segment whose rows the order-th group of 256 workgroups builds
-    uint32_t pad;
-};
-static_assert(sizeof(WtClass) == 64, "WtClass layout");
-
-// The wavelet-tree images: wt_layout (host only) decides whether they apply and lays out the segments (fused: every
-// class must be one segment), wt_launch runs the plan kernel with the classes and zeroed row sums already on the
-// device -- with hints (fused) the kernel computes the correction table itself (FNV of each hint per row L, C-sorted
-// per class) into hints->table and zeroes the two given ranges; wt_build = the separate path (table built first).
-struct WtPlanHints {
-    const uint32_t *hoff;
-    const uint8_t *hbytes;
-    const uint32_t *perm;
-    uint4 *table;
-    uint32_t *zero0;
-    uint32_t n_zero0;
-    uint32_t *zero1;
-    uint32_t n_zero1;
-};
-bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint32_t n_cls, const ModParams &mod,
-               bool fused, std::vector<WtClass> &oc);
-int wt_launch(WtState &w, const uint4 *d_table, uint32_t E, const ModParams &mod, hipStream_t st,
-              const WtPlanHints *hints, WtClass *d_cls, unsigned long long *d_rowsum, bool sync);
-int wt_build(WtState &w, nmz_ctx *ctx, const uint4 *d_table, uint32_t E, const ClassInfo *cls, uint32_t n_cls,
-             const ModParams &mod, hipStream_t st);
-// topk_scratch (wt_topk_scratch_bytes(S), or nullptr): the sweep also leaves per-seed sums (in bucketed order) and
-// per-workgroup largest sums there for wt_topk
-int wt_sweep(const WtState &w, nmz_ctx *ctx, hipStream_t st, const Buckets &b, const uint4 *d_table, uint32_t E,
-             const ModParams &mod, nmz_sched_stats *d_stats, uint64_t S, void *topk_scratch, uint32_t k);
-size_t wt_topk_scratch_bytes(uint64_t S);
-// the top-k (k <= 64) of a sweep that ran with topk_scratch (the sweep zeroes its candidate counter)
-int wt_topk(hipStream_t st, void *scratch, const uint32_t *sorted_idx, uint64_t S, uint64_t seed0, uint32_t k,
-            nmz_topk_entry *d_out);
 
 }  // namespace nmz

@@ -20,6 +20,7 @@
 
 #include "nmz_common.h"
 #include "nmz_internal.h"
+#include "replayable_plan.h"
 #include "topk_dev.h"
 
 namespace nmz {

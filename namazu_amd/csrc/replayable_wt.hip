@@ -28,6 +28,7 @@
 
 #include "nmz_common.h"
 #include "nmz_internal.h"
+#include "replayable_plan.h"
 
 namespace nmz {
 

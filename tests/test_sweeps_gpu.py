@@ -26,19 +26,26 @@ def rep_oracle(seeds, hints, m, n_dump=0):
 
 
 # ---------------------------------------------------------------- K1
-@pytest.fixture(params=["wt", "wt_sep", "wt_bb7", "wt_bb5", "oq"])
+@pytest.fixture(params=["wt", "wt_sep", "wt_bb7", "wt_bb5", "oq", "pd"])
 def k1(ab_knobs, request, monkeypatch):
-    """K1's two statistics kernels: wavelet trees (the default) and order queries (NMZ_REPLAY_WT=0 at plan
-    creation); plans that neither fits take the per-decision sweep either way. "wt" builds the wavelet-tree plan
-    with the fused plan kernel (it computes and C-sorts the correction table itself), "wt_sep" with the separate
-    table, sort and plan kernels (NMZ_WT_FUSED=0, the path for classes of 4,096 events or more). The wavelet plans
-    take the widest rank blocks (at most 64 ranks) whose row image fits LDS; "wt_bb7" / "wt_bb5" set the cap to 128 /
-    32 ranks (NMZ_WT_BB: 32 is the width of larger rows)."""
+    """K1's kernel families: the two statistics kernels -- wavelet trees (the default) and order queries
+    (NMZ_REPLAY_WT=0 at plan creation) -- and the per-decision sweeps, which plans that neither statistics kernel
+    fits take either way. "wt" builds the wavelet-tree plan with the fused plan kernel (it computes and C-sorts the
+    correction table itself), "wt_sep" with the separate table, sort and plan kernels (NMZ_WT_FUSED=0, the path for
+    classes of 4,096 events or more). The wavelet plans take the widest rank blocks (at most 64 ranks) whose row
+    image fits LDS; "wt_bb7" / "wt_bb5" set the cap to 128 / 32 ranks (NMZ_WT_BB: 32 is the width of larger rows).
+    "pd" (NMZ_REPLAY_WT=0 and NMZ_REPLAY_OQ=0, read at every sweep) runs the per-decision sweeps wherever the
+    dispatch allows: k_replayable_sweep_fast and its merge for maxInterval < 2^30, k_replayable_sweep_general from
+    2^32, and still the order-query kernel in between."""
     monkeypatch.delenv("NMZ_WT_FUSED", raising=False)
     monkeypatch.delenv("NMZ_WT_BB", raising=False)
+    monkeypatch.delenv("NMZ_REPLAY_OQ", raising=False)
     if request.param in ("wt_bb7", "wt_bb5"):
         monkeypatch.setenv("NMZ_WT_BB", request.param[-1])
-    if request.param == "oq":
+    if request.param == "pd":
+        monkeypatch.setenv("NMZ_REPLAY_WT", "0")
+        monkeypatch.setenv("NMZ_REPLAY_OQ", "0")
+    elif request.param == "oq":
         monkeypatch.setenv("NMZ_REPLAY_WT", "0")
     else:
         monkeypatch.delenv("NMZ_REPLAY_WT", raising=False)
