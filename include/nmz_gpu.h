@@ -604,6 +604,94 @@ int nmz_unique_traces_dev(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d
                           uint32_t n_traces, uint32_t max_entities, uint64_t *d_sig, uint32_t *d_first_equal,
                           void *stream);
 
+/* ---- replayable policy: delivery-order classes of seeds ---------------------
+ * Replayable.QueueEvent releases every event at arrival + determineInterval(event)
+ * (replayablepolicy.go:100-126), so a seed is a delivery order; `nmz tools visualize` classes runs by the equality
+ * of their orders (cli/tools/visualize.go:51-136). These entry points join the two: which of N seeds deliver
+ * distinct orders, which single seed to replay for each, and which orders the history already holds.
+ * For one trace the caller gives the hints (CSR, n_events), arrival_ns[n_events], max_interval_ns, sym[n_events]
+ * (uint64 event or action symbols, as nmz_trace_signatures takes them) and optionally entity[n_events] (uint32,
+ * NMZ_NONE = skipped, as nmz_unique_traces; NULL = exact mode). For seed s:
+ *     release[s][e] = arrival_ns[e] + delay[s][e]      (delay as nmz_replayable_sweep; 0 when max_interval_ns == 0)
+ *     delivery order pi_s = the counted events sorted by (release asc, event index asc)
+ *     rank[s][e]    = exact mode: position of e in pi_s
+ *                     PO mode:    position of e among the events of its own entity in pi_s
+ *     sig[s]        = the 128-bit signature nmz_trace_signatures gives the trace (sym[pi_s(0)], sym[pi_s(1)], ...)
+ *                     with entity[pi_s(i)], bit for bit (the sum of the (symbol, rank) mixes plus the count terms;
+ *                     entity id values are never read, only the ranks)
+ *     gap           = release difference of two events consecutive in a compared sequence (the whole order in
+ *                     exact mode, each entity's projection in PO mode)
+ *     min_gap_ns[s] = the smallest gap (INT64_MAX when no pair is compared)
+ *     gap_event[s]  = among the pairs attaining it, the smallest event index of the pair's later event
+ *                     (NMZ_NONE when none)
+ * Equal releases are a race in the reference (it sleeps in real time); the tie rule (event index) makes the order
+ * deterministic and min_gap_ns == 0 reports the race. Because sig[s] equals the signature of a recorded run with
+ * the same delivery, predicted and recorded signatures can be classed together (nmz_sig_classes_dev).
+ * Limits, each NMZ_EINVAL with a message: 1 <= n_events <= NMZ_DELIVERY_MAX_EVENTS; 0 <= arrival_ns <= 2^50;
+ * 0 <= max_interval_ns <= 2^50 (release * 4096 + e is then one 63-bit sort key with the tie rule built in);
+ * entity ids < 16384 or NMZ_NONE; max_seeds < 2^32; hint offsets non-decreasing. Equal hints are legal. */
+#define NMZ_DELIVERY_MAX_EVENTS 4096
+
+/* Per-seed result of a delivery sweep, 32 bytes. */
+typedef struct nmz_delivery_stats {
+    uint64_t sig_lo;     /* the signature, as sig[2 i], sig[2 i + 1] of nmz_trace_signatures */
+    uint64_t sig_hi;
+    int64_t min_gap_ns;  /* smallest gap of the compared sequences; INT64_MAX when none      */
+    uint32_t gap_event;  /* the later event of the first pair attaining it; NMZ_NONE if none */
+    uint32_t n_counted;  /* events in the order (n_events minus the NMZ_NONE ones)           */
+} nmz_delivery_stats;
+
+/* One seed on the calling host thread, no device work (replayablepolicy.go:100-126; the signature's classes are
+ * those of visualize.go:51-136): plain FNV-1a over seed || hint, a u64 remainder and a comparison sort, so it
+ * checks the kernel's tables, reductions and sorting network independently. stats may be NULL. order (may be NULL)
+ * receives the delivery order, n_counted event indices followed by NMZ_NONE up to n_events; release_ns (may be NULL)
+ * every event's release. The only form that returns the permutation itself. */
+int nmz_replayable_delivery_host(const uint8_t *seed, uint32_t seed_len, const uint32_t *hint_off,
+                                 const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns,
+                                 const int64_t *arrival_ns, const uint64_t *sym, const uint32_t *entity,
+                                 nmz_delivery_stats *stats, uint32_t *order, int64_t *release_ns);
+/* The plan owns the device tables of one trace (grouped by entity) and the scratch of one sweep of up to max_seeds
+ * (< 2^32) seeds; host arrays are borrowed for the call. It serves one stream at a time; destroy waits for the
+ * plan's sweeps (replayablepolicy.go:100-126). */
+typedef struct nmz_replayable_delivery_plan nmz_replayable_delivery_plan;
+int nmz_replayable_delivery_plan_create(nmz_ctx *ctx, const uint32_t *hint_off, const uint8_t *hint_bytes,
+                                        uint32_t n_events, int64_t max_interval_ns, const int64_t *arrival_ns,
+                                        const uint64_t *sym, const uint32_t *entity /* may be NULL */,
+                                        uint64_t max_seeds, nmz_replayable_delivery_plan **out);
+int nmz_replayable_delivery_plan_destroy(nmz_replayable_delivery_plan *plan);
+/* d_stats[n_seeds] for the seeds "seed_lo" .. "seed_lo + n_seeds - 1" (decimal strings generated on the device,
+ * wrapping past 2^64; replayablepolicy.go:74-87 seed string, :100-126 release times), enqueued on `stream`
+ * (NULL = the context's). */
+int nmz_replayable_delivery_sweep_decimal_dev(nmz_replayable_delivery_plan *plan, uint64_t seed_lo, uint64_t n_seeds,
+                                              nmz_delivery_stats *d_stats, void *stream);
+/* The same for arbitrary seed strings (device CSR d_seed_off[n_seeds + 1] into d_seed_bytes; the empty seed is the
+ * reference's default, replayablepolicy.go:74-81, :100-126). */
+int nmz_replayable_delivery_sweep_dev(nmz_replayable_delivery_plan *plan, const uint32_t *d_seed_off,
+                                      const uint8_t *d_seed_bytes, uint64_t n_seeds, nmz_delivery_stats *d_stats,
+                                      void *stream);
+/* Classes over the stats of a sweep (visualize.go:51-136 equality, on predicted orders): d_first_equal[n] = the
+ * smallest j with an equal signature; d_class_rep[n] (may be NULL) = for a class head h (first_equal[h] == h) the
+ * member with the largest min_gap_ns, ties to the smallest index, the seed to replay for that order, and NMZ_NONE
+ * for every other i; *d_n_classes (may be NULL) = the number of classes. n < 2^31. Enqueued on `stream` (NULL =
+ * the context's); scratch is the context's, so one call at a time per context. */
+int nmz_delivery_classes_dev(nmz_ctx *ctx, const nmz_delivery_stats *d_stats, uint32_t n, uint32_t *d_first_equal,
+                             uint32_t *d_class_rep, uint32_t *d_n_classes, void *stream);
+/* The plain form over d_sig[2 n] (visualize.go:51-136): signatures of recorded runs (nmz_trace_signatures) and
+ * predicted ones (the stats' sig_lo, sig_hi) in one array are classed together. */
+int nmz_sig_classes_dev(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t n, uint32_t *d_first_equal, void *stream);
+/* Host pointers, synchronous: plan + sweep + classes (replayablepolicy.go:100-126, visualize.go:51-136).
+ * stats[n_seeds], first_equal[n_seeds], class_rep[n_seeds] and n_classes may each be NULL. */
+int nmz_replayable_delivery_sweep(nmz_ctx *ctx, const uint32_t *seed_off, const uint8_t *seed_bytes, uint64_t n_seeds,
+                                  const uint32_t *hint_off, const uint8_t *hint_bytes, uint32_t n_events,
+                                  int64_t max_interval_ns, const int64_t *arrival_ns, const uint64_t *sym,
+                                  const uint32_t *entity, nmz_delivery_stats *stats, uint32_t *first_equal,
+                                  uint32_t *class_rep, uint32_t *n_classes);
+int nmz_replayable_delivery_sweep_decimal(nmz_ctx *ctx, uint64_t seed_lo, uint64_t n_seeds, const uint32_t *hint_off,
+                                          const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns,
+                                          const int64_t *arrival_ns, const uint64_t *sym, const uint32_t *entity,
+                                          nmz_delivery_stats *stats, uint32_t *first_equal, uint32_t *class_rep,
+                                          uint32_t *n_classes);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

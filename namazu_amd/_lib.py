@@ -54,6 +54,12 @@ ORDER_STATS_DTYPE = np.dtype([("sat_mask", "<u8"), ("min_slack_ns", "<i8"), ("n_
 assert ORDER_STATS_DTYPE.itemsize == 24
 
 
+# per-seed result of a delivery sweep (nmz_delivery_stats)
+DELIVERY_STATS_DTYPE = np.dtype([("sig_lo", "<u8"), ("sig_hi", "<u8"), ("min_gap_ns", "<i8"), ("gap_event", "<u4"),
+                                 ("n_counted", "<u4")])
+NMZ_DELIVERY_MAX_EVENTS = 4096
+
+
 class NmzLibraryError(RuntimeError):
     """libnmz_gpu.so is missing or failed to load (no CPU fallback exists)."""
 
@@ -135,6 +141,16 @@ SIGNATURES = {
     "nmz_ed_plan_counters": (_int, [_P, _P, _P]),
     "nmz_debug_tp_offsets": (_int, [_P, _P, _u32, _u32, _P, _P, _P, _P]),
     "nmz_ed_plan_query_knn": (_int, [_P, _P, _P, _u32, _u32, _P, _P]),
+    "nmz_replayable_delivery_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
+    "nmz_replayable_delivery_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),
+    "nmz_replayable_delivery_plan_destroy": (_int, [_P]),
+    "nmz_replayable_delivery_sweep_decimal_dev": (_int, [_P, _u64, _u64, _P, _P]),
+    "nmz_replayable_delivery_sweep_dev": (_int, [_P, _P, _P, _u64, _P, _P]),
+    "nmz_delivery_classes_dev": (_int, [_P, _P, _u32, _P, _P, _P, _P]),
+    "nmz_sig_classes_dev": (_int, [_P, _P, _u32, _P, _P]),
+    "nmz_replayable_delivery_sweep": (_int, [_P, _P, _P, _u64, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P, _P]),
+    "nmz_replayable_delivery_sweep_decimal": (_int, [_P, _u64, _u64, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P,
+                                                     _P]),
     "nmz_trace_signatures": (_int, [_P, _P, _P, _P, _u32, _P]),
     "nmz_unique_traces": (_int, [_P, _P, _P, _P, _u32, _P]),
     "nmz_unique_traces_dev": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _P, _P]),

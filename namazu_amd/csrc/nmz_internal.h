@@ -146,6 +146,11 @@ int ed_bv_query_launch(const EdBvQueryArgs &A, uint32_t bw, bool cmp, uint32_t b
 int device_unique_u64(const uint64_t *d_sym, uint64_t total, uint64_t *d_uniq, uint64_t cap, uint64_t *n_uniq,
                       hipStream_t st);
 int ed_bv_launch(const EdBvArgs &A, uint32_t bw, bool cmp, uint64_t blocks, hipStream_t st);
+// unique.hip, for delivery.hip: the per-context table of the signature's rank keys (sig_dev.h; RANK_KEYS entries,
+// built on first use), and the equality classes of d_sig[2 * N]: first[i] = the smallest j with sig_j == sig_i
+// (radix sort with the index as payload; scratch ctx->buf[6]). The caller holds ctx.
+int sig_rank_keys(nmz_ctx *ctx, const ulonglong2 **out);
+int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_first, hipStream_t st);
 
 // wide-band bit-parallel edit distance (ed_wide.hip): one pair per wave
 struct EdWideArgs {

@@ -35,6 +35,7 @@
 
 #include "nmz_common.h"
 #include "nmz_internal.h"
+#include "sig_dev.h"
 
 namespace nmz {
 
@@ -55,39 +56,13 @@ constexpr uint32_t SIG_U = NMZ_SIG_U;  // 64-element steps loaded together per w
 constexpr int SIG_PIPE = NMZ_SIG_PIPE;  // PO modes: the rank-key gather mixed one step later (1) or after the
                                        // batch's ranks (2) (k_trace_sig)
 
-__device__ __forceinline__ uint64_t fmix64(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
-
-// per-rank keys: RANK_KEYS ranks in a table (computed once per context), larger ranks inline
-constexpr uint32_t RANK_KEYS = 65536;
-
-__device__ __forceinline__ uint64_t rank_key_a(uint32_t r) { return fmix64((uint64_t)r + 0x9e3779b97f4a7c15ULL); }
-__device__ __forceinline__ uint64_t rank_key_b(uint32_t r) {
-    return fmix64(((uint64_t)r << 32 | (r ^ 0x5bd1e995u)) + 0x632be59bd9b4e019ULL);
-}
-
 __global__ void k_rank_keys(ulonglong2 *__restrict__ keys) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < RANK_KEYS) keys[r] = make_ulonglong2(rank_key_a(r), rank_key_b(r));
 }
 
-// the pair (symbol s, rank r) -> two 64-bit summands: t = fmix64(s ^ ka(r)) and a second, different nonlinear
-// function of t and kb(r) (one more 64-bit multiply instead of another fmix64)
 __device__ __forceinline__ ulonglong2 rank_keys(uint32_t r, const ulonglong2 *__restrict__ keys) {
     return r < RANK_KEYS ? keys[r] : make_ulonglong2(rank_key_a(r), rank_key_b(r));
-}
-
-__device__ __forceinline__ void mix2k(uint64_t s, ulonglong2 k, uint64_t &a, uint64_t &b) {
-    const uint64_t t = fmix64(s ^ k.x);
-    a = t;
-    const uint64_t u = (t ^ k.y) * 0x94d049bb133111ebULL;
-    b = u ^ (u >> 29);
 }
 
 __device__ __forceinline__ void mix2(uint64_t s, uint32_t r, const ulonglong2 *__restrict__ keys, uint64_t &a,
@@ -248,8 +223,8 @@ __global__ __launch_bounds__(256) void k_trace_sig(const uint64_t *__restrict__ 
         counted += __shfl_xor(counted, o, 64);
     }
     if (lane == 0) {
-        sig[2 * (uint64_t)t] = acc1 + fmix64((uint64_t)counted + 1);
-        sig[2 * (uint64_t)t + 1] = acc2 ^ fmix64(((uint64_t)counted << 1) | 1);
+        sig[2 * (uint64_t)t] = sig_final_lo(acc1, counted);
+        sig[2 * (uint64_t)t + 1] = sig_final_hi(acc2, counted);
     }
 }
 
@@ -288,9 +263,8 @@ __global__ void k_sig_first(const uint32_t *__restrict__ idx_sorted, const uint3
     if (p < N) first_equal[idx_sorted[p]] = idx_sorted[start[p]];
 }
 
-static int sig_launch(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_ent, uint32_t N,
-                      uint32_t max_ent, uint64_t *d_sig, hipStream_t st) {
-    if (N == 0) return NMZ_OK;
+// the per-context rank-key table (RANK_KEYS entries), built on first use; the caller holds ctx
+int sig_rank_keys(nmz_ctx *ctx, const ulonglong2 **out) {
     DevBuf &kb = ctx->buf[14];  // rank keys, built once per context
     if (!kb.ptr) {
         NMZ_TRY(kb.ensure((size_t)RANK_KEYS * sizeof(ulonglong2)));
@@ -299,7 +273,15 @@ static int sig_launch(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym
         NMZ_HIP(hipGetLastError());
         NMZ_HIP(hipStreamSynchronize(ctx->stream));
     }
-    const ulonglong2 *keys = kb.as<ulonglong2>();
+    *out = kb.as<ulonglong2>();
+    return NMZ_OK;
+}
+
+static int sig_launch(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_ent, uint32_t N,
+                      uint32_t max_ent, uint64_t *d_sig, hipStream_t st) {
+    if (N == 0) return NMZ_OK;
+    const ulonglong2 *keys = nullptr;
+    NMZ_TRY(sig_rank_keys(ctx, &keys));
     if (!d_ent) {
         hipLaunchKernelGGL(k_trace_sig<0>, dim3(ceil_div(N, SIG_WAVES)), dim3(64 * SIG_WAVES), 0, st, d_off, d_sym,
                            nullptr, N, 0u, 0u, SIG_WAVES, keys, d_sig);
@@ -323,7 +305,7 @@ static int sig_launch(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym
 }
 
 // equality classes from signatures: first_equal[i] = smallest j with sig_j == sig_i
-static int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_first, hipStream_t st) {
+int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_first, hipStream_t st) {
     if (N == 0) return NMZ_OK;
     size_t sort_bytes = 0, scan_bytes = 0;
     NMZ_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr,

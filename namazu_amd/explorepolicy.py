@@ -85,6 +85,38 @@ class SweepResult:
         self.attrs = attrs  # ProcSet sweeps: the dumped seeds' per-process attributes
 
 
+class DeliveryResult:
+    """Replayable.DeliveryOrders: stats[n] (DELIVERY_STATS_DTYPE), first_equal[n] (the smallest seed index with
+    the same delivery-order signature), class_rep[n] (at a class head: the member with the largest min_gap_ns, ties
+    to the smallest index; NMZ_NONE elsewhere) and n_classes."""
+
+    def __init__(self, stats, first_equal, class_rep, n_classes):
+        self.stats = stats
+        self.first_equal = first_equal
+        self.class_rep = class_rep
+        self.n_classes = n_classes
+
+    def representatives(self, min_gap_ns=0, known_sigs=None):
+        """One seed index per class, its class_rep, in class-head order. Classes whose representative's smallest
+        gap is below min_gap_ns are dropped (the reference sleeps in real time: a closer pair may swap), and so are
+        classes whose signature is in known_sigs ([k][2] uint64 or (lo, hi) pairs, e.g.
+        historystorage.trace_signatures of the stored runs)."""
+        known = set()
+        if known_sigs is not None:
+            known = {(int(lo), int(hi)) for lo, hi in np.asarray(known_sigs, np.uint64).reshape(-1, 2)}
+        out = []
+        heads = np.nonzero(self.first_equal == np.arange(len(self.first_equal)))[0]
+        for h in heads:
+            r = int(self.class_rep[h])
+            st = self.stats[r]
+            if int(st["min_gap_ns"]) < min_gap_ns:
+                continue
+            if (int(st["sig_lo"]), int(st["sig_hi"])) in known:
+                continue
+            out.append(r)
+        return out
+
+
 class ChannelClosed(queue.Empty):
     """ActionChannel.get() on a closed channel (a subclass of queue.Empty, so `except queue.Empty` still catches it;
     a consumer loop that must stop once the channel is closed catches this one first)."""
@@ -538,6 +570,75 @@ class Replayable(ExplorePolicy):
             _lib.ptr(sb), len(seed), _lib.ptr(hoff), _lib.ptr(hb), len(event_hints), int(self.MaxInterval),
             _lib.ptr(arr), _lib.ptr(cons), len(cons), _lib.ptr(stats), _lib.ptr(slack)))
         return stats[0], slack[:len(cons)]
+
+    @staticmethod
+    def _delivery_inputs(hints, arrival_ns, sym, entity):
+        hoff, hb = to_csr(hints)
+        arr = np.ascontiguousarray(arrival_ns, np.int64)
+        sy = np.ascontiguousarray(sym, np.uint64)
+        if len(arr) != len(hints) or len(sy) != len(hints):
+            raise ValueError(f"{len(arr)} arrival times and {len(sy)} symbols for {len(hints)} hints")
+        ent = None
+        if entity is not None:
+            ent = np.ascontiguousarray(entity, np.uint32)
+            if len(ent) != len(hints):
+                raise ValueError(f"{len(ent)} entity ids for {len(hints)} hints")
+        return hoff, hb, arr, sy, ent
+
+    def DeliveryOrders(self, hints, arrival_ns, sym, entity=None, seeds=None, seed_lo=None, n_seeds=None, ctx=None):
+        """Class seeds by the delivery order they produce (nmz_replayable_delivery_sweep[_decimal]).
+
+        QueueEvent releases event e at arrival_ns[e] + determineInterval(e) (replayablepolicy.go:100-126); the order
+        of the releases (ties by event index) is the trace the seed delivers, and two seeds are in one class iff
+        `nmz tools visualize` would call their traces equal (visualize.go:51-136): the same order (entity None) or
+        the same per-entity orders (entity[e] = dense entity id, NMZ_NONE = skipped). sym[e] are the uint64 event
+        (or action) symbols of the trace, as historystorage stores them, so the signatures equal those of recorded
+        runs (historystorage.trace_signatures). Seeds are either `seeds` (strings) or the decimal strings of
+        seed_lo .. seed_lo + n_seeds - 1. Returns a DeliveryResult:
+
+            r = policy.DeliveryOrders(hints, arrival_ns, sym, entity, seeds=seeds)
+            known = historystorage.trace_signatures(storage.load_all())
+            for s in replay.distinct_order_seeds(r, seeds, min_gap_ns=1_000_000, known_sigs=known):
+                env = replay.replay_env(s, os.environ)       # one `nmz run` per new delivery order
+        """
+        ctx = ctx or self._ctx()
+        hoff, hb, arr, sy, ent = self._delivery_inputs(hints, arrival_ns, sym, entity)
+        if (seeds is None) == (seed_lo is None) or (seeds is None) != (n_seeds is not None):
+            raise ValueError("give either seeds or seed_lo and n_seeds")
+        n = len(seeds) if seeds is not None else int(n_seeds)
+        stats = np.zeros(n, _lib.DELIVERY_STATS_DTYPE)
+        first = np.zeros(n, np.uint32)
+        rep = np.zeros(n, np.uint32)
+        nc = np.zeros(1, np.uint32)
+        L = _lib.load()
+        if seeds is not None:
+            soff, sb = to_csr(seeds)
+            _lib.check(L.nmz_replayable_delivery_sweep(
+                ctx.handle, _lib.ptr(soff), _lib.ptr(sb), n, _lib.ptr(hoff), _lib.ptr(hb), len(hints),
+                int(self.MaxInterval), _lib.ptr(arr), _lib.ptr(sy), _lib.ptr(ent), _lib.ptr(stats), _lib.ptr(first),
+                _lib.ptr(rep), _lib.ptr(nc)))
+        else:
+            _lib.check(L.nmz_replayable_delivery_sweep_decimal(
+                ctx.handle, int(seed_lo) & (2**64 - 1), n, _lib.ptr(hoff), _lib.ptr(hb), len(hints),
+                int(self.MaxInterval), _lib.ptr(arr), _lib.ptr(sy), _lib.ptr(ent), _lib.ptr(stats), _lib.ptr(first),
+                _lib.ptr(rep), _lib.ptr(nc)))
+        return DeliveryResult(stats, first, rep, int(nc[0]))
+
+    def delivery_order(self, event_hints, arrival_ns, sym, entity=None):
+        """The delivery of self.Seed on the host (nmz_replayable_delivery_host, no GPU): (order, release_ns, stats)
+        with order = the counted events' indices by (release, index), release_ns[len(hints)] int64 and stats one
+        DELIVERY_STATS_DTYPE record."""
+        hoff, hb, arr, sy, ent = self._delivery_inputs(event_hints, arrival_ns, sym, entity)
+        seed = self.Seed.encode() if isinstance(self.Seed, str) else bytes(self.Seed)
+        sb = np.frombuffer(seed, np.uint8).copy() if seed else np.zeros(1, np.uint8)
+        n = len(event_hints)
+        stats = np.zeros(1, _lib.DELIVERY_STATS_DTYPE)
+        order = np.zeros(max(n, 1), np.uint32)
+        rel = np.zeros(max(n, 1), np.int64)
+        _lib.check(_lib.load().nmz_replayable_delivery_host(
+            _lib.ptr(sb), len(seed), _lib.ptr(hoff), _lib.ptr(hb), n, int(self.MaxInterval), _lib.ptr(arr),
+            _lib.ptr(sy), _lib.ptr(ent), _lib.ptr(stats), _lib.ptr(order), _lib.ptr(rel)))
+        return order[:int(stats[0]["n_counted"])], rel[:n], stats[0]
 
     def decide_intervals(self, events, ctx=None):
         """determineInterval for a batch of events under self.Seed (nmz_replayable_decide)."""

@@ -375,6 +375,25 @@ def first_equal(traces, po_reduction=True, ctx=None):
     return out[:n]
 
 
+def trace_signatures(traces, po_reduction=True, ctx=None):
+    """sig[len(traces)][2] uint64: the 128-bit equality signatures of SingleTraces (nmz_trace_signatures; exact:
+    action symbols, PO: per-entity event sequences, as first_equal). Stored runs' signatures are the known_sigs of
+    DeliveryResult.representatives / replay.distinct_order_seeds: a predicted delivery order with the same
+    signature has already been explored."""
+    ctx = ctx or _lib.default_context()
+    if isinstance(traces, TraceSet):
+        ts, ent = traces, None
+    elif po_reduction:
+        ts, ent = po_inputs(traces)
+    else:
+        ts, ent = TraceSet([t.action_symbols for t in traces]), None
+    n = len(ts)
+    sig = np.zeros((max(n, 1), 2), np.uint64)
+    _lib.check(_lib.load().nmz_trace_signatures(ctx.handle, _lib.ptr(ts.off), _lib.ptr(ts.sym), _lib.ptr(ent), n,
+                                                _lib.ptr(sig)))
+    return sig[:n]
+
+
 def unique_trace_curve(traces, po_reduction=True, ctx=None):
     """visualize.go gnuplot mode (:138-172): after trace i, how many distinct traces have been seen.
     traces: SingleTraces (exact or PO mode), or a TraceSet (exact mode over its symbols)."""

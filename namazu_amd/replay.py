@@ -36,6 +36,12 @@ def _is_sentinel(e):
     return int(e["seed"]) == UINT64_MAX and int(e["sum_delay_ns"]) == INT64_MIN and int(e["n_fault"]) == 0
 
 
+def seed_string(seeds, idx):
+    """The seed string of entry `idx` of the swept seed list (strings, bytes, or integers of a decimal sweep)."""
+    s = seeds[idx]
+    return s.decode() if isinstance(s, bytes) else str(s)
+
+
 def replayable_seeds(topk, seeds):
     """Top-k entries of a replayable sweep over `seeds` -> seed strings, best first."""
     out = []
@@ -43,9 +49,17 @@ def replayable_seeds(topk, seeds):
         idx = int(e["seed"])
         if _is_sentinel(e) or idx >= len(seeds):  # fewer seeds than k
             break
-        s = seeds[idx]
-        out.append(s.decode() if isinstance(s, bytes) else str(s))
+        out.append(seed_string(seeds, idx))
     return out
+
+
+def distinct_order_seeds(result, seeds, min_gap_ns=0, known_sigs=None):
+    """A DeliveryResult (Replayable.DeliveryOrders over `seeds`) -> one seed string per distinct delivery order,
+    the class's representative (largest smallest gap), in class-head order: the NMZ_REPLAY_SEED values worth one
+    `nmz run` each (replay_env). min_gap_ns and known_sigs as DeliveryResult.representatives. For a decimal sweep pass
+    seeds = range(seed_lo, seed_lo + n_seeds)."""
+    reps = result.representatives(min_gap_ns=min_gap_ns, known_sigs=known_sigs)
+    return [seed_string(seeds, r) for r in reps]
 
 
 def random_seeds(topk, seed0, n_seeds):

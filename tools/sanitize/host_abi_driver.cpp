@@ -190,6 +190,73 @@ static void order_cases() {
                                              tk) == NMZ_EINVAL);
 }
 
+// nmz_replayable_delivery_host (replayablepolicy.go:100-126, visualize.go:51-136): orders, ties, skipped events,
+// the limits (4,096 events, entity 16383), optional outputs
+static void delivery_cases() {
+    const uint32_t E = NMZ_DELIVERY_MAX_EVENTS;
+    std::vector<uint32_t> off(E + 1, 0), ent(E), order(E);
+    std::string bytes;
+    std::vector<int64_t> arrival(E), rel(E);
+    std::vector<uint64_t> sym(E);
+    for (uint32_t i = 0; i < E; ++i) {
+        bytes += "h" + std::to_string(i % 1000);
+        off[i + 1] = (uint32_t)bytes.size();
+        arrival[i] = (int64_t)(i / 2) * 1000;
+        sym[i] = 0x9E3779B97F4A7C15ull * i;
+        ent[i] = i % 7 == 0 ? NMZ_NONE : (i % 5 == 0 ? 16383u : i % 3);
+    }
+    const uint8_t *hb = reinterpret_cast<const uint8_t *>(bytes.data());
+    const uint8_t seed[2] = {'4', '2'};
+    nmz_delivery_stats st, st2;
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, E, 100000000, arrival.data(), sym.data(), nullptr, &st,
+                                       order.data(), rel.data()) == NMZ_OK);
+    CHECK(st.n_counted == E && st.min_gap_ns >= 0 && st.gap_event < E);
+    for (uint32_t i = 1; i < E; ++i)
+        CHECK(rel[order[i - 1]] < rel[order[i]] || (rel[order[i - 1]] == rel[order[i]] && order[i - 1] < order[i]));
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, E, (int64_t)1 << 50, arrival.data(), sym.data(),
+                                       ent.data(), &st2, order.data(), nullptr) == NMZ_OK);
+    CHECK(st2.n_counted == E - (E + 6) / 7 && order[st2.n_counted] == NMZ_NONE && order[E - 1] == NMZ_NONE);
+    CHECK(nmz_replayable_delivery_host(nullptr, 0, off.data(), hb, 4, 0, arrival.data(), sym.data(), nullptr, &st,
+                                       order.data(), nullptr) == NMZ_OK);
+    CHECK(st.n_counted == 4 && st.min_gap_ns == 0 && st.gap_event == 1 && order[0] == 0 && order[3] == 3);
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, 1, 5, arrival.data(), sym.data(), nullptr, &st, nullptr,
+                                       nullptr) == NMZ_OK);
+    CHECK(st.n_counted == 1 && st.min_gap_ns == INT64_MAX && st.gap_event == NMZ_NONE);
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, 8, 5, arrival.data(), sym.data(), nullptr, nullptr,
+                                       nullptr, nullptr) == NMZ_OK);
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, 0, 5, arrival.data(), sym.data(), nullptr, &st, nullptr,
+                                       nullptr) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "n_events") != nullptr);
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, 8, ((int64_t)1 << 50) + 1, arrival.data(), sym.data(),
+                                       nullptr, &st, nullptr, nullptr) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "max_interval_ns") != nullptr);
+    ent[3] = 16384;
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, 8, 5, arrival.data(), sym.data(), ent.data(), &st,
+                                       nullptr, nullptr) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "entity[3]") != nullptr);
+    arrival[2] = ((int64_t)1 << 50) + 1;
+    CHECK(nmz_replayable_delivery_host(seed, 2, off.data(), hb, 8, 5, arrival.data(), sym.data(), nullptr, &st, nullptr,
+                                       nullptr) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "arrival_ns[2]") != nullptr);
+    CHECK(nmz_replayable_delivery_host(nullptr, 2, off.data(), hb, 8, 5, arrival.data(), sym.data(), nullptr, &st,
+                                       nullptr, nullptr) == NMZ_EINVAL);
+    // the device entry points reject a NULL context or plan before any device work
+    nmz_replayable_delivery_plan *plan = nullptr;
+    uint32_t u[2];
+    uint64_t sig[2];
+    CHECK(nmz_replayable_delivery_plan_create(nullptr, off.data(), hb, 8, 5, arrival.data(), sym.data(), nullptr, 10,
+                                              &plan) == NMZ_EINVAL);
+    CHECK(nmz_replayable_delivery_plan_destroy(nullptr) == NMZ_OK);
+    CHECK(nmz_replayable_delivery_sweep_decimal_dev(nullptr, 0, 1, &st, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_replayable_delivery_sweep_dev(nullptr, nullptr, nullptr, 0, &st, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_delivery_classes_dev(nullptr, &st, 1, u, u, u, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_sig_classes_dev(nullptr, sig, 1, u, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_replayable_delivery_sweep(nullptr, off.data(), hb, 1, off.data(), hb, 8, 5, arrival.data(), sym.data(),
+                                        nullptr, &st, u, u, u) == NMZ_EINVAL);
+    CHECK(nmz_replayable_delivery_sweep_decimal(nullptr, 0, 1, off.data(), hb, 8, 5, arrival.data(), sym.data(),
+                                                nullptr, &st, u, u, u) == NMZ_EINVAL);
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -238,6 +305,7 @@ int main() {
     null_ctx_cases();
     procset_cases();
     order_cases();
+    delivery_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
