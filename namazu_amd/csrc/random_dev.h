@@ -80,6 +80,13 @@ __device__ __forceinline__ uint4 uniform4(uint4 v) {
 // nm = -M31 and one = 1 arrive in VGPRs the compiler cannot see through, so that both conditional corrections are
 // a VOP2 borrow (v_sub_co) plus a VCC v_cndmask with VGPR operands (full rate) rather than an add of a literal and
 // a v_min_u32 (half rate), and the s == 0 test is a borrow out of s - 1 rather than a v_cmp.
+// Each correction fires about once in 2^31 decisions; the searched vectors of tests/golden/go_seed_edges.json
+// (tools/find_go_seed_edges.c) take them, by class: the fold at s1 == M31 exactly and next to it (k0_s1_m31m1,
+// k0_s1_m31, k0_s1_m31p1, k1_s1_m31, k2_s1_m31); the 4k borrow (k1_s1_m31, k1_t3, k2_s1_m31, k2_t7; wrap only and
+// sign only for k = 1; t classes folded and, for a seed with Hm = 0, unfolded); the zero map (k0_s1_m31, k1_t4,
+// k2_t8); s = 1 and s = M31 - 1 going into modmul / modmul_shl8 (k0_s1_m31p1, k1_t5, k2_t9; k0_s1_m31m1, k1_t3,
+// k2_t7). tests/test_go_seed_edges_gpu.py runs them: test_random_sweep_on_the_vectors (both k_random_sweep
+// instantiations, nm and one in VGPRs) and test_procset_on_the_vectors (k_procset_sweep, the default arguments).
 __device__ __forceinline__ uint32_t go_seed_from_table(uint64_t H, uint32_t Hm, uint4 q,
                                                        uint32_t nm = gorand::NEG_M31, uint32_t one = 1u) {
     const uint64_t C = ((uint64_t)q.y << 32) | q.x;
