@@ -15,7 +15,10 @@ RNG = np.random.default_rng(0xED)
 
 
 def make_traces(n, lmin, lmax, mut, alphabet=12, rng=RNG):
-    base = rng.integers(0, alphabet, size=max(lmax, 1))
+    """n traces, each a prefix of one random base (length in [lmin, lmax]) with substitutions at rate `mut`. Every
+    pair of them aligns on the main diagonal plus a tail (all indels sit at the end): alignments that leave the
+    diagonal are the business of tests/ed_cases.py and tests/test_ed_offdiag_gpu.py."""
+    base =rng.integers(0, alphabet, size=max(lmax, 1))
     out = []
     for _ in range(n):
         l = int(rng.integers(lmin, lmax + 1))
