@@ -692,6 +692,97 @@ int nmz_replayable_delivery_sweep_decimal(nmz_ctx *ctx, uint64_t seed_lo, uint64
                                           nmz_delivery_stats *stats, uint32_t *first_equal, uint32_t *class_rep,
                                           uint32_t *n_classes);
 
+/* ---- replayable policy: seeds nearest to a recorded delivery order -----------
+ * A recorded failing run usually has no seed (the random policy reseeds from the clock, util/queue/impl.go:39);
+ * the replayable policy reproduces a run only from a known seed (replayablepolicy.go:63-126). These entry points
+ * answer: among N replayable seeds, which deliver the events in the order nearest to the recorded one?
+ * For one trace the caller gives the hints (CSR, n_events), arrival_ns[n_events] and max_interval_ns as the
+ * delivery sweep takes them, optionally entity[n_events] (NULL = exact mode, NMZ_NONE = skipped), and
+ * target_pos[n_events] (uint32): the event's position in the recorded order, NMZ_NONE if the recorded run does not
+ * contain it. An event is counted iff target_pos != NMZ_NONE and, in PO mode, entity != NMZ_NONE. The target_pos
+ * of counted events must be distinct; they need not be dense (only their order is read).
+ * Releases, the delivery order pi_s of the counted events (release asc, event index asc) and the compared sequences
+ * (the whole order in exact mode, each entity's projection in PO mode) are the delivery sweep's above. For seed s:
+ *     n_discordant = #{(a, b) in one compared sequence : target_pos[a] < target_pos[b] and b precedes a in pi_s}
+ *                    (Kendall tau distance; PO mode counts same-entity pairs only, the pairs tracesEqualInPO sees)
+ *     in place     = event e's rank in its compared sequence in pi_s equals its rank there by target_pos
+ *     prefix_len   = how many leading events of the target order (counted events by target_pos ascending) are all
+ *                    in place: the common prefix of pi_s and the target (exact), the longest target prefix every
+ *                    entity sees unchanged (PO); the notion of HistoryStorage.Search(prefix),
+ *                    historystorage/naive/naive.go:235-257. Equals n_counted when the orders match.
+ *     min_gap_ns, gap_event = as nmz_delivery_stats, over the counted events
+ *     n_in_place   = events in place
+ * n_discordant == 0 <=> every compared sequence is in target order <=> the seed's delivery signature
+ * (nmz_delivery_stats over the same counted events) equals the recorded run's.
+ * The plan reports n_counted and n_pairs = the sum over the compared sequences of n (n - 1) / 2 (<= 8,386,560).
+ * Ranking is written as nmz_topk_entry (sentinel and .seed as the order sweep's lists, so nmz_topk_merge_dev and
+ * namazu_amd/replay.py serve it unchanged):
+ *     NMZ_TARGET_RANK_PAIRS:  n_fault = n_pairs - n_discordant, sum_delay_ns = min_gap_ns, first_fault = prefix_len
+ *     NMZ_TARGET_RANK_PREFIX: n_fault = prefix_len, sum_delay_ns = n_pairs - n_discordant, first_fault = n_in_place
+ * Limits, each NMZ_EINVAL with a message: those of the delivery sweep (1 <= n_events <= 4096; arrivals and
+ * max_interval_ns in [0, 2^50]; entity ids < 16384 or NMZ_NONE; max_seeds < 2^32; hint offsets non-decreasing);
+ * a target_pos that appears twice among the counted events; an unknown rank mode. With nothing counted or
+ * max_interval_ns == 0 every seed has the same record. */
+#define NMZ_TARGET_RANK_PAIRS 0
+#define NMZ_TARGET_RANK_PREFIX 1
+
+/* Per-seed result of a nearest-order sweep, 24 bytes. */
+typedef struct nmz_target_stats {
+    uint32_t n_discordant; /* pairs delivered the other way round than the target orders them */
+    uint32_t prefix_len;   /* leading events of the target order that are all in place         */
+    int64_t min_gap_ns;    /* smallest gap of the compared sequences; INT64_MAX when none      */
+    uint32_t gap_event;    /* the later event of the first pair attaining it; NMZ_NONE if none */
+    uint32_t n_in_place;   /* events whose rank equals their target rank                       */
+} nmz_target_stats;
+
+/* One seed on the calling host thread, no device work (replayablepolicy.go:100-126 release times;
+ * historystorage/naive/naive.go:235-257 the prefix): plain FNV-1a over seed || hint, a u64 remainder, a comparison
+ * sort and a merge count per sequence; it shares no table or reduction with the kernel. stats, n_counted and
+ * n_pairs may each be NULL. Vets a candidate seed before a replay. */
+int nmz_replayable_target_host(const uint8_t *seed, uint32_t seed_len, const uint32_t *hint_off,
+                               const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns,
+                               const int64_t *arrival_ns, const uint32_t *entity /* may be NULL */,
+                               const uint32_t *target_pos, nmz_target_stats *stats, uint32_t *n_counted,
+                               uint32_t *n_pairs);
+/* The plan owns the device tables of one trace and target and the scratch of one sweep of up to max_seeds (< 2^32)
+ * seeds; host arrays are borrowed for the call. It serves one stream at a time; destroy waits for the plan's sweeps
+ * (replayablepolicy.go:100-126, historystorage/naive/naive.go:235-257). */
+typedef struct nmz_replayable_target_plan nmz_replayable_target_plan;
+int nmz_replayable_target_plan_create(nmz_ctx *ctx, const uint32_t *hint_off, const uint8_t *hint_bytes,
+                                      uint32_t n_events, int64_t max_interval_ns, const int64_t *arrival_ns,
+                                      const uint32_t *entity /* may be NULL */, const uint32_t *target_pos,
+                                      uint64_t max_seeds, nmz_replayable_target_plan **out);
+int nmz_replayable_target_plan_destroy(nmz_replayable_target_plan *plan);
+/* The plan's constants (replayablepolicy.go:100-126, naive.go:235-257): each pointer may be NULL. */
+int nmz_replayable_target_plan_info(const nmz_replayable_target_plan *plan, uint32_t *n_counted, uint32_t *n_pairs);
+/* The seeds "seed_lo" .. "seed_lo + n_seeds - 1" (decimal strings generated on the device, wrapping past 2^64;
+ * replayablepolicy.go:74-87 seed string, :100-126 release times; naive.go:235-257), enqueued on `stream` (NULL = the
+ * context's). d_stats[n_seeds] may be NULL: the sweep then writes only d_topk[k] (k <= 256; k == 0: no top-k).
+ * Top-k .seed = the seed's integer value. */
+int nmz_replayable_target_sweep_decimal_dev(nmz_replayable_target_plan *plan, uint64_t seed_lo, uint64_t n_seeds,
+                                            int rank_mode, uint32_t k, nmz_target_stats *d_stats /* may be NULL */,
+                                            nmz_topk_entry *d_topk, void *stream);
+/* The same for arbitrary seed strings (device CSR d_seed_off[n_seeds + 1] into d_seed_bytes; the empty seed is the
+ * reference's default, replayablepolicy.go:74-81, :100-126; naive.go:235-257). Top-k .seed = seed0 + the seed's
+ * index. */
+int nmz_replayable_target_sweep_dev(nmz_replayable_target_plan *plan, const uint32_t *d_seed_off,
+                                    const uint8_t *d_seed_bytes, uint64_t n_seeds, uint64_t seed0, int rank_mode,
+                                    uint32_t k, nmz_target_stats *d_stats /* may be NULL */, nmz_topk_entry *d_topk,
+                                    void *stream);
+/* Host pointers, synchronous: plan + sweep + top-k (replayablepolicy.go:100-126, naive.go:235-257). stats[n_seeds],
+ * topk[k] (k <= 256), n_counted and n_pairs may each be NULL. Top-k .seed = the seed's index in the CSR, or its
+ * integer value for the decimal form. */
+int nmz_replayable_target_sweep(nmz_ctx *ctx, const uint32_t *seed_off, const uint8_t *seed_bytes, uint64_t n_seeds,
+                                const uint32_t *hint_off, const uint8_t *hint_bytes, uint32_t n_events,
+                                int64_t max_interval_ns, const int64_t *arrival_ns, const uint32_t *entity,
+                                const uint32_t *target_pos, int rank_mode, uint32_t k, nmz_target_stats *stats,
+                                nmz_topk_entry *topk, uint32_t *n_counted, uint32_t *n_pairs);
+int nmz_replayable_target_sweep_decimal(nmz_ctx *ctx, uint64_t seed_lo, uint64_t n_seeds, const uint32_t *hint_off,
+                                        const uint8_t *hint_bytes, uint32_t n_events, int64_t max_interval_ns,
+                                        const int64_t *arrival_ns, const uint32_t *entity, const uint32_t *target_pos,
+                                        int rank_mode, uint32_t k, nmz_target_stats *stats, nmz_topk_entry *topk,
+                                        uint32_t *n_counted, uint32_t *n_pairs);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

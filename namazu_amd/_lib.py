@@ -58,6 +58,12 @@ assert ORDER_STATS_DTYPE.itemsize == 24
 DELIVERY_STATS_DTYPE = np.dtype([("sig_lo", "<u8"), ("sig_hi", "<u8"), ("min_gap_ns", "<i8"), ("gap_event", "<u4"),
                                  ("n_counted", "<u4")])
 NMZ_DELIVERY_MAX_EVENTS = 4096
+# per-seed result of a nearest-order sweep (nmz_target_stats) and its rank modes
+TARGET_STATS_DTYPE = np.dtype([("n_discordant", "<u4"), ("prefix_len", "<u4"), ("min_gap_ns", "<i8"),
+                               ("gap_event", "<u4"), ("n_in_place", "<u4")])
+assert TARGET_STATS_DTYPE.itemsize == 24
+NMZ_TARGET_RANK_PAIRS, NMZ_TARGET_RANK_PREFIX = 0, 1
+TARGET_RANK_MODES = {"pairs": NMZ_TARGET_RANK_PAIRS, "prefix": NMZ_TARGET_RANK_PREFIX}
 
 
 class NmzLibraryError(RuntimeError):
@@ -151,6 +157,16 @@ SIGNATURES = {
     "nmz_replayable_delivery_sweep": (_int, [_P, _P, _P, _u64, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P, _P]),
     "nmz_replayable_delivery_sweep_decimal": (_int, [_P, _u64, _u64, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P,
                                                      _P]),
+    "nmz_replayable_target_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
+    "nmz_replayable_target_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),
+    "nmz_replayable_target_plan_destroy": (_int, [_P]),
+    "nmz_replayable_target_plan_info": (_int, [_P, _P, _P]),
+    "nmz_replayable_target_sweep_decimal_dev": (_int, [_P, _u64, _u64, _int, _u32, _P, _P, _P]),
+    "nmz_replayable_target_sweep_dev": (_int, [_P, _P, _P, _u64, _u64, _int, _u32, _P, _P, _P]),
+    "nmz_replayable_target_sweep": (_int, [_P, _P, _P, _u64, _P, _P, _u32, _i64, _P, _P, _P, _int, _u32, _P, _P, _P,
+                                           _P]),
+    "nmz_replayable_target_sweep_decimal": (_int, [_P, _u64, _u64, _P, _P, _u32, _i64, _P, _P, _P, _int, _u32, _P,
+                                                   _P, _P, _P]),
     "nmz_trace_signatures": (_int, [_P, _P, _P, _P, _u32, _P]),
     "nmz_unique_traces": (_int, [_P, _P, _P, _P, _u32, _P]),
     "nmz_unique_traces_dev": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _P, _P]),

@@ -117,6 +117,16 @@ class DeliveryResult:
         return out
 
 
+class TargetResult(SweepResult):
+    """Replayable.NearestOrders: stats[n] (TARGET_STATS_DTYPE, or None), topk[k] (TOPK_DTYPE, or None) and the
+    plan's constants n_counted (events compared) and n_pairs (pairs compared: n_discordant's range)."""
+
+    def __init__(self, stats, topk, n_counted, n_pairs):
+        super().__init__(stats, topk=topk)
+        self.n_counted = n_counted
+        self.n_pairs = n_pairs
+
+
 class ChannelClosed(queue.Empty):
     """ActionChannel.get() on a closed channel (a subclass of queue.Empty, so `except queue.Empty` still catches it;
     a consumer loop that must stop once the channel is closed catches this one first)."""
@@ -639,6 +649,95 @@ class Replayable(ExplorePolicy):
             _lib.ptr(sb), len(seed), _lib.ptr(hoff), _lib.ptr(hb), n, int(self.MaxInterval), _lib.ptr(arr),
             _lib.ptr(sy), _lib.ptr(ent), _lib.ptr(stats), _lib.ptr(order), _lib.ptr(rel)))
         return order[:int(stats[0]["n_counted"])], rel[:n], stats[0]
+
+    @staticmethod
+    def _target_inputs(hints, arrival_ns, target_order, target_pos, entity):
+        hoff, hb = to_csr(hints)
+        n = len(hints)
+        arr = np.ascontiguousarray(arrival_ns, np.int64)
+        if len(arr) != n:
+            raise ValueError(f"{len(arr)} arrival times for {n} hints")
+        if (target_order is None) == (target_pos is None):
+            raise ValueError("give either target_order or target_pos")
+        if target_order is not None:
+            order = np.asarray(target_order, np.int64).reshape(-1)
+            if len(order) and (order.min() < 0 or order.max() >= n):
+                raise ValueError(f"target_order holds an event index outside [0, {n})")
+            if len(np.unique(order)) != len(order):
+                raise ValueError("target_order holds an event twice")
+            tp = np.full(n, _lib.NMZ_NONE, np.uint32)
+            tp[order] = np.arange(len(order), dtype=np.uint32)
+        else:
+            tp = np.ascontiguousarray(target_pos, np.uint32)
+            if len(tp) != n:
+                raise ValueError(f"{len(tp)} target positions for {n} hints")
+        ent = None
+        if entity is not None:
+            ent = np.ascontiguousarray(entity, np.uint32)
+            if len(ent) != n:
+                raise ValueError(f"{len(ent)} entity ids for {n} hints")
+        return hoff, hb, arr, tp, ent
+
+    def NearestOrders(self, hints, arrival_ns, target_order=None, target_pos=None, entity=None, seeds=None,
+                      seed_lo=None, n_seeds=None, k=0, rank_by="pairs", want_stats=True, ctx=None):
+        """Rank seeds by how near their delivery order is to a recorded run (nmz_replayable_target_sweep[_decimal]).
+
+        QueueEvent releases event e at arrival_ns[e] + determineInterval(e) (replayablepolicy.go:100-126); the order
+        of the releases (ties by event index) is the trace the seed delivers. The recorded order is target_order
+        (event indices in recorded order; events it leaves out are not counted) or target_pos (uint32 per event, its
+        position in the recorded order, NMZ_NONE = absent; distinct, not necessarily dense). entity as
+        DeliveryOrders (None = the whole order is compared, else each entity's projection). Seeds are either `seeds`
+        (strings; top-k seed = index) or the decimal strings of seed_lo .. seed_lo + n_seeds - 1 (top-k seed = the
+        integer). Returns a TargetResult: stats[n_seeds] (TARGET_STATS_DTYPE: n_discordant = pairs delivered the
+        other way round, prefix_len = the reproduced prefix of the recorded order as HistoryStorage.Search(prefix)
+        reads it, min_gap_ns / gap_event = the room against timer jitter, n_in_place; None unless want_stats),
+        topk[k] (TOPK_DTYPE, best first), n_counted and n_pairs. rank_by = "pairs": fewest discordant pairs, then
+        the largest smallest gap (n_fault = n_pairs - n_discordant, sum_delay_ns = min_gap_ns, first_fault =
+        prefix_len); "prefix": longest prefix, then fewest discordant pairs (n_fault = prefix_len, sum_delay_ns =
+        n_pairs - n_discordant, first_fault = n_in_place). From a failing run in the storage to seeds to replay:
+
+            tp = historystorage.match_target(sym, arrival_ns, failing.symbols)   # failing: the stored SingleTrace
+            r = policy.NearestOrders(hints, arrival_ns, target_pos=tp, seeds=seeds, k=8, want_stats=False)
+            env = replay.replay_env(replay.replayable_seeds(r.topk, seeds)[0], os.environ)
+        """
+        ctx = ctx or self._ctx()
+        hoff, hb, arr, tp, ent = self._target_inputs(hints, arrival_ns, target_order, target_pos, entity)
+        if rank_by not in _lib.TARGET_RANK_MODES:
+            raise ValueError(f"rank_by must be one of {sorted(_lib.TARGET_RANK_MODES)}, got {rank_by!r}")
+        if (seeds is None) == (seed_lo is None) or (seeds is None) != (n_seeds is not None):
+            raise ValueError("give either seeds or seed_lo and n_seeds")
+        n = len(seeds) if seeds is not None else int(n_seeds)
+        stats = np.zeros(n, _lib.TARGET_STATS_DTYPE) if want_stats else None
+        topk = np.zeros(k, _lib.TOPK_DTYPE) if k else None
+        info = np.zeros(2, np.uint32)
+        mode = _lib.TARGET_RANK_MODES[rank_by]
+        L = _lib.load()
+        if seeds is not None:
+            soff, sb = to_csr(seeds)
+            _lib.check(L.nmz_replayable_target_sweep(
+                ctx.handle, _lib.ptr(soff), _lib.ptr(sb), n, _lib.ptr(hoff), _lib.ptr(hb), len(hints),
+                int(self.MaxInterval), _lib.ptr(arr), _lib.ptr(ent), _lib.ptr(tp), mode, k, _lib.ptr(stats),
+                _lib.ptr(topk), _lib.ptr(info[0:1]), _lib.ptr(info[1:2])))
+        else:
+            _lib.check(L.nmz_replayable_target_sweep_decimal(
+                ctx.handle, int(seed_lo) & (2**64 - 1), n, _lib.ptr(hoff), _lib.ptr(hb), len(hints),
+                int(self.MaxInterval), _lib.ptr(arr), _lib.ptr(ent), _lib.ptr(tp), mode, k, _lib.ptr(stats),
+                _lib.ptr(topk), _lib.ptr(info[0:1]), _lib.ptr(info[1:2])))
+        return TargetResult(stats, topk, int(info[0]), int(info[1]))
+
+    def target_distance(self, event_hints, arrival_ns, target_pos, entity=None):
+        """The distance of self.Seed's delivery order to a recorded run on the host (nmz_replayable_target_host, no
+        GPU): (stats, n_counted, n_pairs) with stats one TARGET_STATS_DTYPE record. Vets a candidate seed before a
+        replay."""
+        hoff, hb, arr, tp, ent = self._target_inputs(event_hints, arrival_ns, None, target_pos, entity)
+        seed = self.Seed.encode() if isinstance(self.Seed, str) else bytes(self.Seed)
+        sb = np.frombuffer(seed, np.uint8).copy() if seed else np.zeros(1, np.uint8)
+        stats = np.zeros(1, _lib.TARGET_STATS_DTYPE)
+        info = np.zeros(2, np.uint32)
+        _lib.check(_lib.load().nmz_replayable_target_host(
+            _lib.ptr(sb), len(seed), _lib.ptr(hoff), _lib.ptr(hb), len(event_hints), int(self.MaxInterval),
+            _lib.ptr(arr), _lib.ptr(ent), _lib.ptr(tp), _lib.ptr(stats), _lib.ptr(info[0:1]), _lib.ptr(info[1:2])))
+        return stats[0], int(info[0]), int(info[1])
 
     def decide_intervals(self, events, ctx=None):
         """determineInterval for a batch of events under self.Seed (nmz_replayable_decide)."""

@@ -399,3 +399,40 @@ def unique_trace_curve(traces, po_reduction=True, ctx=None):
     traces: SingleTraces (exact or PO mode), or a TraceSet (exact mode over its symbols)."""
     fe = first_equal(traces, po_reduction, ctx)
     return list(np.cumsum(fe == np.arange(len(fe))).astype(int))
+
+
+def match_target(sym, arrival_ns, recorded_sym):
+    """target_pos[len(sym)] (uint32) of a trace's events against a recorded run's symbol sequence, the input of
+    Replayable.NearestOrders: the i-th recorded occurrence of a symbol is matched to the i-th earliest-arriving
+    event of the trace with that symbol (arrival ties go to the smaller index), and the event's target position is
+    the occurrence's index in recorded_sym. Events without a recorded occurrence get NMZ_NONE; recorded occurrences
+    without an event leave a hole (positions need not be dense). Pure numpy."""
+    sym = np.asarray(sym, np.uint64).reshape(-1)
+    rec = np.asarray(recorded_sym, np.uint64).reshape(-1)
+    arr = np.asarray(arrival_ns, np.int64).reshape(-1)
+    if len(arr) != len(sym):
+        raise ValueError(f"{len(arr)} arrival times for {len(sym)} symbols")
+    out = np.full(len(sym), _lib.NMZ_NONE, np.uint32)
+    if not len(sym) or not len(rec):
+        return out
+
+    def occurrence(order, s):
+        """Per element (in `order`): how many earlier elements of `order` carry the same symbol."""
+        by_sym = order[np.argsort(s[order], kind="stable")]  # grouped by symbol, `order` kept inside a group
+        g = s[by_sym]
+        start = np.r_[0, np.nonzero(g[1:] != g[:-1])[0] + 1]
+        occ = np.arange(len(g)) - np.repeat(start, np.diff(np.r_[start, len(g)]))
+        return by_sym, occ
+
+    ev, ev_occ = occurrence(np.lexsort((np.arange(len(sym)), arr)), sym)  # by (arrival, index)
+    rc, rc_occ = occurrence(np.arange(len(rec)), rec)
+    # join on (symbol, occurrence): both sides sorted by symbol then occurrence
+    ek = np.stack([sym[ev], ev_occ.astype(np.uint64)], axis=1)
+    rk = np.stack([rec[rc], rc_occ.astype(np.uint64)], axis=1)
+    ekv = np.ascontiguousarray(ek).view([("s", "<u8"), ("o", "<u8")]).reshape(-1)
+    rkv = np.ascontiguousarray(rk).view([("s", "<u8"), ("o", "<u8")]).reshape(-1)
+    at = np.searchsorted(rkv, ekv)
+    hit = at < len(rkv)
+    hit[hit] = rkv[at[hit]] == ekv[hit]
+    out[ev[hit]] = rc[at[hit]].astype(np.uint32)
+    return out
