@@ -783,6 +783,65 @@ int nmz_replayable_target_sweep_decimal(nmz_ctx *ctx, uint64_t seed_lo, uint64_t
                                         int rank_mode, uint32_t k, nmz_target_stats *stats, nmz_topk_entry *topk,
                                         uint32_t *n_counted, uint32_t *n_pairs);
 
+/* ---- order contrast: the event pairs whose order separates failing runs from passing ones ------------
+ * A history storage holds many recorded runs, each labelled by its result.json (IsSuccessful,
+ * historystorage/naive/naive.go:199-213; `nmz tools summary` prints the failing ones, cli/tools/summary.go:40-57).
+ * These entry points answer: which few ordered event pairs are released one way round in the failing runs and the
+ * other way round in the passing ones? Those pairs are the constraints nmz_replayable_order_sweep* takes.
+ * For one event universe (the trace whose hints the sweeps take) the caller gives
+ *     pos[n_runs][n_events]  uint32, row-major: the position of event e in recorded run r, NMZ_NONE if the run does
+ *                            not hold it; any other value is legal and positions need not be dense (one
+ *                            match_target row per run, namazu_amd/historystorage.py)
+ *     failed[n_runs]         uint8, 1 = the run failed, 0 = it passed.
+ * With n_fail and n_pass the numbers of failing and passing runs, for every ordered pair (b, a), b != a:
+ *     F(b,a) = #{failing r : pos[r][b] != NONE, pos[r][a] != NONE, pos[r][b] < pos[r][a]}
+ *     P(b,a) = the same over the passing runs
+ *     score(b,a) = F(b,a) * n_pass - P(b,a) * n_fail        (int64; = n_fail n_pass (F / n_fail - P / n_pass))
+ * Two events at equal positions in a run count for neither direction. Pairs are ranked by (score desc, F desc,
+ * b * n_events + a asc), a strict total order; only pairs with score > 0 are listed, and past them the list holds
+ * the sentinel {NMZ_NONE, NMZ_NONE, INT64_MIN, 0, 0, 0, 0}. n_positive is the number of ordered pairs with score > 0.
+ * Limits, each NMZ_EINVAL with a message: 1 <= n_events <= NMZ_DELIVERY_MAX_EVENTS; 1 <= n_runs <=
+ * NMZ_CONTRAST_MAX_RUNS (two 16-bit counts pack into one word, n_fail n_pass < 2^32, every score fits int64 with
+ * INT64_MIN free); failed[r] in {0, 1}; at least one failing and one passing run; k <= 256. */
+#define NMZ_CONTRAST_MAX_RUNS 65535
+
+/* One listed pair, 32 bytes: failing runs release `before` ahead of `after`. */
+typedef struct nmz_order_pair {
+    uint32_t before, after;
+    int64_t score;
+    uint32_t n_fail_with, n_pass_with;       /* F(before, after), P(before, after) */
+    uint32_t n_fail_against, n_pass_against; /* F(after, before), P(after, before) */
+} nmz_order_pair;
+/* Counts of one ordered pair, at [b * n_events + a]; the diagonal is 0. */
+typedef struct nmz_pair_counts {
+    uint32_t n_fail_with, n_pass_with;
+} nmz_pair_counts;
+typedef struct nmz_contrast_info {
+    uint32_t n_fail, n_pass;
+    uint64_t n_positive;
+} nmz_contrast_info;
+
+/* One pair on the calling host thread, no device work (naive.go:199-213 IsSuccessful, cli/tools/summary.go:40-57):
+ * plain loops over the runs by the definition above; it shares no code with the kernels. Checks every limit above
+ * and before != after, both < n_events. out and info may each be NULL; info->n_positive is 0 (one pair says nothing
+ * about the others). Serves the CPU tests, and vets a pair before hours of replays are spent on it. */
+int nmz_order_contrast_host(const uint32_t *pos, const uint8_t *failed, uint32_t n_runs, uint32_t n_events,
+                            uint32_t before, uint32_t after, nmz_order_pair *out, nmz_contrast_info *info);
+/* Device pointers, enqueued on `stream` (NULL = the context's); scratch from the context, which serves one contrast
+ * at a time (naive.go:199-213, cli/tools/summary.go:40-57). d_counts[n_events * n_events] may be NULL: nothing of
+ * size n_events^2 is then written or allocated (the hot form). d_pairs[k] (k <= 256; k == 0: no list) and d_info are
+ * written on the stream. The sizes and k are checked before any launch; the labels are on the device and are not
+ * read by the host: any nonzero label counts as failing, and with no failing or no passing run every score is 0,
+ * the list is all sentinels and n_positive is 0 (d_info still reports n_fail and n_pass). */
+int nmz_order_contrast_dev(nmz_ctx *ctx, const uint32_t *d_pos, const uint8_t *d_failed, uint32_t n_runs,
+                           uint32_t n_events, uint32_t k, nmz_pair_counts *d_counts /* may be NULL */,
+                           nmz_order_pair *d_pairs, nmz_contrast_info *d_info, void *stream);
+/* Host pointers, synchronous, built on the _dev form (naive.go:199-213, cli/tools/summary.go:40-57). Every limit
+ * above, the labels included, is checked before any device work. counts, pairs and info may each be NULL. */
+int nmz_order_contrast(nmz_ctx *ctx, const uint32_t *pos, const uint8_t *failed, uint32_t n_runs, uint32_t n_events,
+                       uint32_t k, nmz_pair_counts *counts /* may be NULL */, nmz_order_pair *pairs,
+                       nmz_contrast_info *info);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

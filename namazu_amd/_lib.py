@@ -64,6 +64,13 @@ TARGET_STATS_DTYPE = np.dtype([("n_discordant", "<u4"), ("prefix_len", "<u4"), (
 assert TARGET_STATS_DTYPE.itemsize == 24
 NMZ_TARGET_RANK_PAIRS, NMZ_TARGET_RANK_PREFIX = 0, 1
 TARGET_RANK_MODES = {"pairs": NMZ_TARGET_RANK_PAIRS, "prefix": NMZ_TARGET_RANK_PREFIX}
+# order contrast: one listed pair (nmz_order_pair), one ordered pair's counts (nmz_pair_counts), nmz_contrast_info
+ORDER_PAIR_DTYPE = np.dtype([("before", "<u4"), ("after", "<u4"), ("score", "<i8"), ("n_fail_with", "<u4"),
+                             ("n_pass_with", "<u4"), ("n_fail_against", "<u4"), ("n_pass_against", "<u4")])
+assert ORDER_PAIR_DTYPE.itemsize == 32
+PAIR_COUNTS_DTYPE = np.dtype([("n_fail_with", "<u4"), ("n_pass_with", "<u4")])
+CONTRAST_INFO_DTYPE = np.dtype([("n_fail", "<u4"), ("n_pass", "<u4"), ("n_positive", "<u8")])
+NMZ_CONTRAST_MAX_RUNS = 65535
 
 
 class NmzLibraryError(RuntimeError):
@@ -165,6 +172,9 @@ SIGNATURES = {
     "nmz_replayable_target_sweep_dev": (_int, [_P, _P, _P, _u64, _u64, _int, _u32, _P, _P, _P]),
     "nmz_replayable_target_sweep": (_int, [_P, _P, _P, _u64, _P, _P, _u32, _i64, _P, _P, _P, _int, _u32, _P, _P, _P,
                                            _P]),
+    "nmz_order_contrast_host": (_int, [_P, _P, _u32, _u32, _u32, _u32, _P, _P]),
+    "nmz_order_contrast_dev": (_int, [_P, _P, _P, _u32, _u32, _u32, _P, _P, _P, _P]),
+    "nmz_order_contrast": (_int, [_P, _P, _P, _u32, _u32, _u32, _P, _P, _P]),
     "nmz_replayable_target_sweep_decimal": (_int, [_P, _u64, _u64, _P, _P, _u32, _i64, _P, _P, _P, _int, _u32, _P,
                                                    _P, _P, _P]),
     "nmz_trace_signatures": (_int, [_P, _P, _P, _P, _u32, _P]),

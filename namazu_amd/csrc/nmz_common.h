@@ -85,7 +85,7 @@ struct nmz_ctx {
     std::mutex mu;
     int n_cu = 0;
     // scratch slots reused across calls (host-pointer entry points)
-    nmz::DevBuf buf[18];
+    nmz::DevBuf buf[20];
     std::vector<nmz::DevBuf> pool;  // free plan buffers (DevBuf::pool), freed by nmz_close
     nmz::HostPin pin[2];             // pinned staging of plan inputs ([0] replayable plan, [1] its wavelet classes)
     bool wt_lds_attr = false;        // the wavelet-tree kernels' LDS attribute is set on this context's device

@@ -235,6 +235,36 @@ class Naive(HistoryStorage):
     def AllPairsKNN(self, k, band):
         return allpairs_knn(self.load_all(), k, band)
 
+    # ---- order contrast ----------------------------------------------------------
+    def OrderContrast(self, sym, arrival_ns, k=64, want_counts=False, ctx=None):
+        """The event pairs whose order separates this storage's failing runs from its passing ones
+        (order_contrast). Every stored run is loaded and labelled with IsSuccessful (naive.go:199-213); a run whose
+        result cannot be read is skipped, as `nmz tools summary` does (cli/tools/summary.go:47-51). (sym,
+        arrival_ns) is the event universe: the trace whose hints the sweeps take. Returns a ContrastResult whose
+        run_ids are the stored runs used, in row order. From the storage to a replay:
+
+            c = storage.OrderContrast(sym, arrival_ns, k=64)
+            cons = replay.constraints_from_pairs(c.pairs, 1_000_000, per_event=2)
+            r = policy.OrderSweep(hints, arrival_ns, cons, seeds=seeds, k=8, want_stats=False)
+            best = replay.replayable_seeds(r.topk, seeds)
+            env = replay.replay_env(best[0], os.environ)                     # NMZ_REPLAY_SEED for `nmz run`
+        """
+        ids, runs, failed = [], [], []
+        for i in range(self.NrStoredHistories()):
+            ok, err = self.IsSuccessful(i)
+            if err is not None:
+                continue
+            t, err = self.GetStoredHistory(i)
+            if err is not None:
+                raise RuntimeError(f"failed to get history {i}: {err}")  # naive.go:241 panics
+            ids.append(i)
+            runs.append(t)
+            failed.append(0 if ok else 1)
+        pos = run_positions(sym, arrival_ns, runs)
+        c = order_contrast(pos, np.array(failed, np.uint8), k=k, want_counts=want_counts, ctx=ctx)
+        c.run_ids = ids
+        return c
+
 
 def New(name, dir_path):
     """historystorage.go:54-62. Returns (storage, error)."""
@@ -436,3 +466,88 @@ def match_target(sym, arrival_ns, recorded_sym):
     hit[hit] = rkv[at[hit]] == ekv[hit]
     out[ev[hit]] = rc[at[hit]].astype(np.uint32)
     return out
+
+
+# ---- order contrast: which event pairs separate failing runs from passing ones -----------------------------
+class ContrastResult:
+    """order_contrast's result: pairs[k] (ORDER_PAIR_DTYPE, best first by (score desc, n_fail_with desc,
+    before * E + after asc); the sentinel {NMZ_NONE, NMZ_NONE, INT64_MIN, 0, 0, 0, 0} past the pairs with
+    score > 0), counts[E][E] (PAIR_COUNTS_DTYPE at [before][after], diagonal 0; None unless asked for), n_fail,
+    n_pass and n_positive (the number of ordered pairs with score > 0)."""
+
+    def __init__(self, pairs, counts, n_fail, n_pass, n_positive):
+        self.pairs = pairs
+        self.counts = counts
+        self.n_fail = n_fail
+        self.n_pass = n_pass
+        self.n_positive = n_positive
+        self.run_ids = None  # Naive.OrderContrast: the stored runs behind the rows
+
+
+def _contrast_inputs(pos, failed):
+    pos = np.ascontiguousarray(pos, np.uint32)
+    if pos.ndim != 2:
+        raise ValueError(f"pos must be [runs][events], got shape {pos.shape}")
+    failed = np.asarray(failed)
+    if failed.dtype == np.bool_:
+        failed = failed.astype(np.uint8)
+    elif failed.size and (failed.min() < 0 or failed.max() > 255):
+        raise ValueError("failed holds a label outside uint8")
+    failed = np.ascontiguousarray(failed, np.uint8).reshape(-1)
+    if len(failed) != pos.shape[0]:
+        raise ValueError(f"{len(failed)} labels for {pos.shape[0]} runs")
+    return pos, failed
+
+
+def run_positions(sym, arrival_ns, traces):
+    """pos[len(traces)][len(sym)] (uint32): one match_target row per recorded run (SingleTraces or event-symbol
+    arrays) against the event universe (sym, arrival_ns) -- the trace whose hints the sweeps take. pos[r][e] is the
+    position of event e in run r, NMZ_NONE if the run does not hold it: order_contrast's input."""
+    sym = np.asarray(sym, np.uint64).reshape(-1)
+    out = np.full((len(traces), len(sym)), _lib.NMZ_NONE, np.uint32)
+    for r, t in enumerate(traces):
+        out[r] = match_target(sym, arrival_ns, t.symbols if isinstance(t, SingleTrace) else t)
+    return out
+
+
+def order_contrast(pos, failed, k=64, want_counts=False, ctx=None):
+    """The ordered event pairs (before, after) released that way round in the failing runs and the other way round
+    in the passing ones (nmz_order_contrast; semantics in include/nmz_gpu.h and DESIGN.md section 2). pos[R][E] as
+    run_positions gives it, failed[R] 0 / 1 (or bool). For every ordered pair F = failing runs that hold both events
+    and release `before` first, P = the same over passing runs, score = F * n_pass - P * n_fail. Returns a
+    ContrastResult with the k best pairs; want_counts adds every pair's (F, P) -- E^2 records, off by default.
+    From a storage to a replay:
+
+        pos = historystorage.run_positions(sym, arrival_ns, runs)            # runs: the stored SingleTraces
+        c = historystorage.order_contrast(pos, failed, k=64)                 # failed: not IsSuccessful, per run
+        cons = replay.constraints_from_pairs(c.pairs, 1_000_000, per_event=2)
+        r = policy.OrderSweep(hints, arrival_ns, cons, seeds=seeds, k=8, want_stats=False)
+        env = replay.replay_env(replay.replayable_seeds(r.topk, seeds)[0], os.environ)   # NMZ_REPLAY_SEED
+    """
+    pos, failed = _contrast_inputs(pos, failed)
+    R, E = pos.shape
+    k = int(k)
+    if not 0 <= k < 2**32:
+        raise ValueError(f"k = {k} does not fit uint32")
+    ctx = ctx or _lib.default_context()
+    pairs = np.zeros(k, _lib.ORDER_PAIR_DTYPE)
+    counts = np.zeros((E, E), _lib.PAIR_COUNTS_DTYPE) if want_counts else None
+    info = np.zeros(1, _lib.CONTRAST_INFO_DTYPE)
+    _lib.check(_lib.load().nmz_order_contrast(ctx.handle, _lib.ptr(pos), _lib.ptr(failed), R, E, k, _lib.ptr(counts),
+                                              _lib.ptr(pairs) if k else None, _lib.ptr(info)))
+    return ContrastResult(pairs, counts, int(info[0]["n_fail"]), int(info[0]["n_pass"]), int(info[0]["n_positive"]))
+
+
+def order_pair(pos, failed, before, after):
+    """One ordered pair on the host (nmz_order_contrast_host, no GPU): (pair, n_fail, n_pass) with pair one
+    ORDER_PAIR_DTYPE record holding both directions' counts. Plain loops that share nothing with the kernels: the
+    check of order_contrast, and the way to vet a pair before replays are spent on it."""
+    pos, failed = _contrast_inputs(pos, failed)
+    R, E = pos.shape
+    out = np.zeros(1, _lib.ORDER_PAIR_DTYPE)
+    info = np.zeros(1, _lib.CONTRAST_INFO_DTYPE)
+    if not (0 <= int(before) < 2**32 and 0 <= int(after) < 2**32):
+        raise ValueError(f"event indices ({before}, {after}) do not fit uint32")
+    _lib.check(_lib.load().nmz_order_contrast_host(_lib.ptr(pos), _lib.ptr(failed), R, E, int(before), int(after),
+                                                   _lib.ptr(out), _lib.ptr(info)))
+    return out[0], int(info[0]["n_fail"]), int(info[0]["n_pass"])

@@ -21,6 +21,7 @@ from .config import Config
 REPLAY_SEED_ENV = "NMZ_REPLAY_SEED"  # replayablepolicy.go:83
 UINT64_MAX = (1 << 64) - 1
 INT64_MIN = -(1 << 63)
+NMZ_NONE = 0xFFFFFFFF
 
 
 def as_int64(seed):
@@ -60,6 +61,40 @@ def distinct_order_seeds(result, seeds, min_gap_ns=0, known_sigs=None):
     seeds = range(seed_lo, seed_lo + n_seeds)."""
     reps = result.representatives(min_gap_ns=min_gap_ns, known_sigs=known_sigs)
     return [seed_string(seeds, r) for r in reps]
+
+
+def constraints_from_pairs(pairs, margin_ns, max_constraints=64, per_event=None):
+    """Listed pairs of historystorage.order_contrast (ORDER_PAIR_DTYPE, best first) -> (before, after, margin_ns)
+    tuples for Replayable.OrderSweep, best first: "release `before` at least margin_ns ahead of `after`", the order
+    the failing runs show. Stops at the sentinel and at max_constraints (OrderSweep takes 64 at most); drops a pair
+    whose reverse was already taken (both cannot hold); with per_event keeps at most that many constraints naming
+    one event -- the top of the list is otherwise often one cause seen through its neighbours. From a storage to a
+    replay:
+
+        c = storage.OrderContrast(sym, arrival_ns, k=64)                     # labelled runs -> discriminating pairs
+        cons = replay.constraints_from_pairs(c.pairs, 1_000_000, per_event=2)
+        r = policy.OrderSweep(hints, arrival_ns, cons, seeds=seeds, k=8, want_stats=False)
+        best = replay.replayable_seeds(r.topk, seeds)
+        env = replay.replay_env(best[0], os.environ)                         # NMZ_REPLAY_SEED for `nmz run`
+    """
+    if per_event is not None and per_event < 1:
+        raise ValueError("per_event must be at least 1")
+    out, taken, uses = [], set(), {}
+    for p in pairs:
+        if len(out) >= max_constraints:
+            break
+        b, a = int(p["before"]), int(p["after"])
+        if b == NMZ_NONE and a == NMZ_NONE and int(p["score"]) == INT64_MIN:
+            break
+        if (a, b) in taken or (b, a) in taken:
+            continue
+        if per_event is not None and (uses.get(b, 0) >= per_event or uses.get(a, 0) >= per_event):
+            continue
+        taken.add((b, a))
+        uses[b] = uses.get(b, 0) + 1
+        uses[a] = uses.get(a, 0) + 1
+        out.append((b, a, int(margin_ns)))
+    return out
 
 
 def random_seeds(topk, seed0, n_seeds):
