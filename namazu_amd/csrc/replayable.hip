@@ -255,8 +255,8 @@ static bool use_oq(const nmz_replayable_plan *p) {
     return p->oq.on && (replay_oq_enabled() || p->mod.kind != MOD_FAST);
 }
 
-// top-k on the wavelet-tree path: candidates above the k-th largest workgroup maximum (NMZ_WT_TOPK=0: the general
-// selection, for A/B runs)
+// top-k on the wavelet-tree path: the seeds of the chunks at or above the k-th largest chunk maximum
+// (NMZ_WT_TOPK=0: the general selection, for A/B runs)
 static bool wt_topk_enabled() {
     static const bool on = [] {
         const char *e = ab_env("NMZ_WT_TOPK");
@@ -271,8 +271,7 @@ static bool wt_topk_enabled() {
 // prepared set `pre` (bucketed already at the statistics kernels' granularity).
 static int replayable_stats(nmz_replayable_plan *p, hipStream_t st, const uint32_t *d_soff,
                             const uint8_t *d_sbytes, uint64_t S, nmz_sched_stats *d_stats, uint64_t dec_lo = 0,
-                            void *wt_topk_scratch = nullptr, uint32_t k = 0,
-                            const nmz_replayable_seeds *pre = nullptr) {
+                            void *wt_topk_scratch = nullptr, const nmz_replayable_seeds *pre = nullptr) {
     if (S == 0) return NMZ_OK;
     const uint32_t E = p->n_events;
     if (E == 0 || p->mod.kind == MOD_ZERO) {
@@ -296,7 +295,7 @@ static int replayable_stats(nmz_replayable_plan *p, hipStream_t st, const uint32
         }
         if (stats_kernel) NMZ_TRY(bucket_seeds_counted(st, sc.h0, S, OQ_WG, sc.b, sc.counter));
     }
-    if (wt) return wt_sweep(p->wt, p->ctx, st, sc.b, p->d_table, E, p->mod, d_stats, S, wt_topk_scratch, k);
+    if (wt) return wt_sweep(p->wt, p->ctx, st, sc.b, p->d_table, E, p->mod, d_stats, S, wt_topk_scratch);
     if (stats_kernel) return oq_sweep(p->oq, p->ctx, st, sc.b, p->d_table, E, p->mod, d_stats);
     return pd_sweep(p, st, sc, S, d_stats);
 }
@@ -348,17 +347,16 @@ static int replayable_run_on(nmz_replayable_plan *p, hipStream_t st, const uint3
                              uint64_t dec_lo, const nmz_replayable_seeds *pre) {
     NMZ_CHECK(k <= 256, "top-k supports k <= 256");
     NMZ_CHECK(k == 0 || d_topk, "d_topk is NULL");
-    // the wavelet-tree sweep's own candidates (k <= 64; more than one general-selection list, so that the gated
-    // fallback has its merge levels): the general selection runs only when they overflow
+    // the wavelet-tree sweep's own top-k (k <= 64): the sweep leaves one record per 64-seed chunk in the plan's
+    // scratch (O(S / 64) records, every one written by the sweep: nothing to reset), and one selection kernel takes
+    // the k best from the chunks at or above the k-th largest chunk maximum, reading their sums from d_stats. Larger
+    // k, other sweeps and NMZ_WT_TOPK=0 take the general selection over the stats
     const bool fused = k && k <= 64 && S > 0 && use_wt(p) && wt_topk_enabled();
-    if (fused) {
-        NMZ_TRY(p->wt_topk.ensure(wt_topk_scratch_bytes(S)));  // the sweep zeroes its candidate counter
-    }
-    NMZ_TRY(replayable_stats(p, st, d_soff, d_sbytes, S, d_stats, dec_lo, fused ? p->wt_topk.ptr : nullptr, k, pre));
-    if (fused) {  // the seeds' order of the sweep that ran (the prepared set's, or this plan's own bucketing)
-        const uint32_t *sidx = pre ? pre->sc.b.sorted_idx
-                                   : carve_seed_scratch(p->seed_scratch.ptr, p->max_seeds).b.sorted_idx;
-        return wt_topk(st, p->wt_topk.ptr, sidx, S, seed0, k, d_topk);
+    if (fused) NMZ_TRY(p->wt_topk.ensure(wt_topk_scratch_bytes(S)));
+    NMZ_TRY(replayable_stats(p, st, d_soff, d_sbytes, S, d_stats, dec_lo, fused ? p->wt_topk.ptr : nullptr, pre));
+    if (fused) {  // the bucketing of the sweep that ran (the prepared set's, or this plan's own)
+        const Buckets b = pre ? pre->sc.b : carve_seed_scratch(p->seed_scratch.ptr, p->max_seeds).b;
+        return wt_topk(st, p->wt_topk.ptr, b.offset, b.sorted_idx, d_stats, S, seed0, k, d_topk);
     }
     if (k) {
         NMZ_TRY(p->topk_lists.ensure(topk_scratch_entries(S, k) * sizeof(nmz_topk_entry)));

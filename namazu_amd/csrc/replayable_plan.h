@@ -133,14 +133,15 @@ int wt_launch(WtState &w, const uint4 *d_table, uint32_t E, const ModParams &mod
               const WtPlanHints *hints, WtClass *d_cls, unsigned long long *d_rowsum, bool sync);
 int wt_build(WtState &w, nmz_ctx *ctx, const uint4 *d_table, uint32_t E, const ClassInfo *cls, uint32_t n_cls,
              const ModParams &mod, hipStream_t st);
-// topk_scratch (wt_topk_scratch_bytes(S), or nullptr): the sweep also leaves per-seed sums (in bucketed order) and
-// per-workgroup largest sums there for wt_topk
+// topk_scratch (wt_topk_scratch_bytes(S), or nullptr): the sweep also leaves one record per 64-seed chunk there for
+// wt_topk (the chunk's largest sum, its first sorted position and its seed count)
 int wt_sweep(const WtState &w, nmz_ctx *ctx, hipStream_t st, const Buckets &b, const uint4 *d_table, uint32_t E,
-             const ModParams &mod, nmz_sched_stats *d_stats, uint64_t S, void *topk_scratch, uint32_t k);
+             const ModParams &mod, nmz_sched_stats *d_stats, uint64_t S, void *topk_scratch);
 size_t wt_topk_scratch_bytes(uint64_t S);
-// the top-k (k <= 64) of a sweep that ran with topk_scratch (the sweep zeroes its candidate counter)
-int wt_topk(hipStream_t st, void *scratch, const uint32_t *sorted_idx, uint64_t S, uint64_t seed0, uint32_t k,
-            nmz_topk_entry *d_out);
+// the top-k (k <= 64) of a sweep that ran with topk_scratch: one kernel, from the chunk records, the sweep's bucketing
+// (bucket_off [257], sorted_idx [S]) and its stats
+int wt_topk(hipStream_t st, void *scratch, const uint32_t *bucket_off, const uint32_t *sorted_idx,
+            const nmz_sched_stats *d_stats, uint64_t S, uint64_t seed0, uint32_t k, nmz_topk_entry *d_out);
 
 // ---- per-decision sweeps (replayable_pd.hip): k_replayable_sweep_fast + k_replayable_merge for m < 2^30,
 // k_replayable_sweep_general otherwise; buckets the hashes sc.h0 (sc.b.hist holds their row counts) at its own
@@ -166,7 +167,7 @@ struct nmz_replayable_plan {
     nmz::DevBuf plan_mem;
     nmz::OqState oq;                    // order-query statistics (k_replayable_sweep_oq)
     nmz::WtState wt;                    // wavelet-tree statistics (k_replayable_sweep_wt, the default when it fits)
-    nmz::DevBuf wt_topk;                // their top-k candidates (sums, workgroup maxima, candidates)
+    nmz::DevBuf wt_topk;                // their top-k scratch (candidates, chunk records)
     // every pooled buffer of the plan: plan_create assigns their pool, plan_destroy_locked releases them
     std::array<nmz::DevBuf *, 8> buffers() {
         return {&plan_mem, &seed_scratch, &partial, &topk_lists, &oq.mem, &wt.mem, &wt.aux, &wt_topk};

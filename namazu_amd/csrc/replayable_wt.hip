@@ -881,21 +881,26 @@ __device__ __forceinline__ void wt_seed_class(const WtVConst &vc, const WtClass 
 
 // ---------------------------------------------------------------------------------------------------------------
 // top-k on the wavelet-tree path (k <= 64; order: sum desc as int64, seed asc; n_fault = 0 for this policy).
-// Each workgroup's largest sum is the largest of a group of seeds, and the groups are disjoint, so the k-th largest
-// of the group maxima (or of a subset of them) is a value at least k seeds reach: no seed below it is in the top k.
-// One kernel (every block derives tau itself: cheaper than a launch) appends the seeds at or above tau (hundreds to
-// a few thousand), and a one-block kernel sorts them (bitonic, LDS); more than WT_CAND candidates (heavy ties, e.g.
-// maxInterval 1) take a slow exact selection there instead. The candidate
-// counter resets itself. (A "last block" handing tau or the ranking to the final workgroup of a kernel needs
-// device-scope fences, i.e. L2 writebacks on every XCD: +40 us on the sweep.)
+// The sweep leaves one record per chunk of 64 seeds: the chunk's largest sum (as an order-preserving key), the sorted
+// position of its first seed and its seed count, at slot chunk_base[L] + ch (chunk_base[L] = the chunks of the rows
+// before L, derived from bucket_off by the sweep and by the selection alike). Every slot of [0, n_chunks) is written
+// exactly once per launch and none beyond is read: no init pass, no device-scope atomic, no fence. The chunks are
+// disjoint groups of seeds, so the k-th largest chunk maximum tau is a value at least k seeds reach: no seed below it
+// is in the top k, and only the seeds of the ~k chunks at or above tau need looking at. One one-block kernel
+// (k_wt_topk_chunks) finds tau (a radix select over the chunk keys), reads those chunks' sums from the caller's
+// stats, sorts the candidates (bitonic, LDS) and writes the k entries; more than WT_CAND flagged chunks or
+// candidates (heavy ties, e.g. maxInterval 1) take a slow exact selection over the stats instead.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr uint32_t WT_CAND = 4096;
-constexpr uint32_t WT_MAX_GROUPS = 256 * 8;
+constexpr int WT_NS = 1;  // seeds per lane of the sweep: its chunks hold 64 WT_NS seeds
+struct WtChunkRec {
+    unsigned long long key;  // the chunk's largest sum ^ 2^63
+    uint32_t pos, cnt;       // sorted position of the chunk's first seed; its seeds
+};
+static_assert(sizeof(WtChunkRec) == 16, "WtChunkRec layout");
 struct WtTopkState {
-    uint32_t n_cand, pad[3];
-    unsigned long long gmax[WT_MAX_GROUPS];
     unsigned long long cand_key[WT_CAND];
-    unsigned long long cand_idx[WT_CAND];
+    uint32_t cand_idx[WT_CAND];
 };
 
 #ifdef WT_TRACE
@@ -936,21 +941,22 @@ __global__ __launch_bounds__(1024) NMZ_WT_ATTR void k_replayable_sweep_wt(
     const uint4 *__restrict__ blob, uint32_t rb16, const unsigned long long *__restrict__ rowsum,
     const WtClass *__restrict__ classes, uint32_t n_classes, uint32_t m, uint64_t mu, uint32_t m_k64, uint32_t msh,
     uint32_t G, nmz_sched_stats *__restrict__ stats, unsigned long long *__restrict__ span,
-    uint64_t *__restrict__ sums, WtTopkState *__restrict__ tk, uint32_t k) {
+    WtChunkRec *__restrict__ rec) {
     constexpr uint32_t CS = 64 * NS;  // seeds per chunk
     extern __shared__ uint4 wt_lds[];
     const uint32_t L = blockIdx.x / G, g = blockIdx.x % G;
     const uint32_t s0 = bucket_off[L], s1 = bucket_off[L + 1];
     const uint32_t nch = (s1 - s0 + CS - 1) / CS;
     const uint32_t c0 = g * nch / G, c1 = (g + 1) * nch / G;
-    uint32_t *ctr = reinterpret_cast<uint32_t *>(wt_lds + rb16);
-    if (tk && blockIdx.x == 0 && threadIdx.x == 0) tk->n_cand = 0;  // the top-k scan after this sweep appends
-    if (c0 == c1) {  // no seeds (an empty group: the smallest key)
-        if (tk && threadIdx.x == 0) tk->gmax[blockIdx.x] = 0ull;
-        return;
-    }
+    uint32_t *ctr = reinterpret_cast<uint32_t *>(wt_lds + rb16);  // [0] the chunk counter, [4..7] chunk_base parts
+    if (c0 == c1) return;  // no chunks (and no records) of this group
     if (span && threadIdx.x == 0) atomicMax(span, ~(unsigned long long)wall_clock64());
     WT_TSTAMP(9);
+    // chunk_base[L], the chunks of the rows before L: the first 256 threads add up a row's chunks each (loaded here,
+    // under the staging), their waves leave partial sums in LDS before the staging's barrier
+    uint32_t cb = 0;
+    if (rec)
+        for (uint32_t t = threadIdx.x; t < L; t += blockDim.x) cb += (bucket_off[t + 1] - bucket_off[t] + CS - 1) / CS;
     {
         const uint4 *__restrict__ src = blob + (uint64_t)L * rb16;
         // every load of a pass in flight at once (indices clamped to the image, stores unconditional)
@@ -963,12 +969,15 @@ __global__ __launch_bounds__(1024) NMZ_WT_ATTR void k_replayable_sweep_wt(
 #pragma unroll
             for (uint32_t k = 0; k < B; ++k) wt_lds[min(i0 + k * nt + threadIdx.x, rb16 - 1)] = v[k];
         }
-        if (threadIdx.x == 0) {
-            *ctr = c0;
-            ctr[2] = ctr[3] = 0;  // the workgroup's largest sum key
+        if (threadIdx.x == 0) *ctr = c0;
+        if (rec && threadIdx.x < 256) {
+            for (int o = 32; o; o >>= 1) cb += __shfl_xor(cb, o, 64);
+            if ((threadIdx.x & 63) == 0) ctr[4 + (threadIdx.x >> 6)] = cb;
+            if (threadIdx.x < 4 && threadIdx.x >= nt / 64) ctr[4 + threadIdx.x] = 0;  // fewer than four waves
         }
     }
     __syncthreads();
+    const uint32_t cbase = rec ? __builtin_amdgcn_readfirstlane(ctr[4] + ctr[5] + ctr[6] + ctr[7]) : 0u;
     WT_TSTAMP(0);
 #ifdef WT_TRACE
     uint32_t n_done = 0;
@@ -1030,8 +1039,6 @@ __global__ __launch_bounds__(1024) NMZ_WT_ATTR void k_replayable_sweep_wt(
             if (j < s1) {
                 const uint64_t kk = total ^ (1ull << 63);
                 km = kk > km ? kk : km;
-                if (sums) sums[j] = total;  // in sorted order: the wave's 64 writes coalesce (by seed index they
-                                            // scatter, one 64-B line per seed: +20 us on the step)
                 nmz_sched_stats st;
                 st.sum_delay_ns = total;
                 st.max_delay_ns = (int64_t)(key[u] >> 32);
@@ -1042,22 +1049,24 @@ __global__ __launch_bounds__(1024) NMZ_WT_ATTR void k_replayable_sweep_wt(
                 stats[idx[u]] = st;
             }
         }
-        if (tk) {
+        if (rec) {  // the chunk's record, one 16-byte store
             for (int o = 32; o; o >>= 1) {
                 const uint64_t v = __shfl_xor(km, o, 64);
                 km = v > km ? v : km;
             }
-            if (lane == 0) atomicMax(reinterpret_cast<unsigned long long *>(ctr + 2), (unsigned long long)km);
+            const uint32_t p = s0 + ch * CS;
+            if (lane == 0)
+                reinterpret_cast<uint4 *>(rec)[cbase + ch] =
+                    make_uint4((uint32_t)km, (uint32_t)(km >> 32), p, min(CS, s1 - p));
         }
 #ifdef WT_TRACE
         if (++n_done <= 8) WT_TSTAMP(n_done);
 #endif
         ch = chn;
     }
-    if (span || tk) {
+    if (span) {
         __syncthreads();
-        if (span && threadIdx.x == 0) atomicMax(span + 1, (unsigned long long)wall_clock64());
-        if (tk && threadIdx.x == 0) tk->gmax[blockIdx.x] = *reinterpret_cast<const unsigned long long *>(ctr + 2);
+        if (threadIdx.x == 0) atomicMax(span + 1, (unsigned long long)wall_clock64());
     }
 }
 
@@ -1065,114 +1074,52 @@ __device__ __forceinline__ bool wt_better(unsigned long long ka, uint64_t sa, un
     return ka > kb || (ka == kb && sa < sb);
 }
 
-// every block: tau = the k-th largest key of min(n, 512) groups sampled evenly over all rows (a subset's k-th largest
-// is at most the whole set's, so tau stays a value at least k seeds reach; ~k n / 512 of the groups' maxima lie
-// above it), by counting; then a grid-stride scan of the sweep's sums appending the seeds at or above tau (hundreds
-// to a few thousand: a row whose sums peak high holds many seeds near its peak). (The first 256 groups alone -- a few rows -- let one configs[1] trace in 17 overflow the
-// candidate list into the slow exact selection: 50 ms.)
-__global__ __launch_bounds__(256) void k_wt_topk_scan(const uint64_t *__restrict__ sums,
-                                                      const uint32_t *__restrict__ sorted_idx, uint64_t S, uint32_t n,
-                                                      uint32_t k, WtTopkState *__restrict__ tk) {
-    constexpr uint32_t PF = 16;  // sums per thread loaded before they are needed (their latency overlaps tau)
-    constexpr uint32_t NS = 512;  // sampled groups
-    __shared__ unsigned long long g[NS];
-    __shared__ unsigned long long tau_s;
-    const uint32_t m = min(n, NS);
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    uint64_t v[PF];
-#pragma unroll
-    for (uint32_t r = 0; r < PF; ++r) {
-        const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x + r * stride;
-        v[r] = i < S ? sums[i] : 0ull;
-    }
-    for (uint32_t i = threadIdx.x; i < m; i += 256) g[i] = tk->gmax[(uint64_t)i * n / m];
-    // fewer groups than k: every seed is a candidate (tau 0); else the k-th largest sampled maximum = the smallest
-    // of those with fewer than k others above them (one count per value, no tie count)
-    if (threadIdx.x == 0) tau_s = m >= k ? ~0ull : 0ull;
-    __syncthreads();
-    if (m >= k) {
-        unsigned long long best = ~0ull;
-        for (uint32_t i = threadIdx.x; i < m; i += 256) {
-            const unsigned long long x = g[i];
-            uint32_t gt = 0;
-#pragma unroll 8
-            for (uint32_t j = 0; j < m; ++j) gt += g[j] > x;
-            if (gt < k) best = x < best ? x : best;
-        }
-        if (best != ~0ull) atomicMin(&tau_s, best);
-    }
-    __syncthreads();
-    const unsigned long long t = tau_s;
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // the block's candidates of one round of PF sums per thread are counted in registers and block-scanned, and ONE
-    // returning atomic per block reserves their range: a returning atomic per candidate wave (the previous form,
-    // hundreds to thousands on one word at ~11 ns each) serialised the scan
-    __shared__ uint32_t wsum[4], base_s;
-    for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < S; i0 += PF * stride) {
-        uint32_t flags = 0;
-#pragma unroll
-        for (uint32_t r = 0; r < PF; ++r) {
-            const uint64_t i = i0 + threadIdx.x + r * stride;
-            if (i0 != (uint64_t)blockIdx.x * 256) v[r] = i < S ? sums[i] : 0ull;  // past the first PF rounds
-            const unsigned long long key = v[r] ^ (1ull << 63);
-            flags |= (i < S && key >= t) ? 1u << r : 0u;
-        }
-        const uint32_t n = __popc(flags);
-        uint32_t a = n;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t x = __shfl_up(a, d, 64);
-            if (lane >= d) a += x;
-        }
-        if (lane == 63) wsum[w] = a;
-        __syncthreads();
-        uint32_t pre = 0, total = 0;
-        for (uint32_t x = 0; x < 4; ++x) {
-            pre += x < w ? wsum[x] : 0u;
-            total += wsum[x];
-        }
-        if (total) {
-            if (threadIdx.x == 0) base_s = atomicAdd(&tk->n_cand, total);
-            __syncthreads();
-            uint32_t pos = base_s + pre + a - n;
-#pragma unroll
-            for (uint32_t r = 0; r < PF; ++r) {
-                if (flags >> r & 1u) {
-                    if (pos < WT_CAND) {
-                        const uint64_t i = i0 + threadIdx.x + r * stride;
-                        tk->cand_key[pos] = v[r] ^ (1ull << 63);
-                        tk->cand_idx[pos] = sorted_idx[i];
-                    }
-                    ++pos;
-                }
-            }
-        }
-        __syncthreads();  // wsum and base_s are rewritten by the next round
-    }
-}
-
-// one block: sort the candidates and write the top k (past WT_CAND candidates -- heavy ties, e.g. maxInterval 1 --
-// select them one rank at a time over every seed: exact, slow); resets the candidate counter
+// The selection, one workgroup: (a) n_chunks from bucket_off, as the sweep derives its slots; (b) tau = the k-th
+// largest chunk key, by a radix select over 8-bit digits with an LDS histogram, starting below the highest bit in
+// which any two keys differ (sums are non-negative and small: four digit passes at configs[1]), or 0 when there are
+// fewer chunks than k; (c) the chunks at or above tau are listed in LDS and their seeds' sums read from the stats,
+// the seeds at or above tau become the candidates (counter in LDS); (d) the candidates sorted and the k entries
+// written; (e) more than WT_CAND flagged chunks or candidates: the exact selection one rank at a time over the stats
+// in seed order.
+// Chunk keys: the first WT_SEL_KPT per thread stay in registers over the digit passes (33 x 512 threads cover
+// configs[1]'s ~16,600 chunks), the rest are read again; reading all of them again on every pass took the kernel
+// alone from 36 to 60 us. One CU's memory throughput bounds the kernel (alone ~32 us: 266 KB of records, then
+// ~6,000 scattered stats rows); beside the neighbouring steps' sweeps it costs the pipelined step ~1-2 us.
+// Static LDS 26.7 KB (27,312 B: the sort's 25.5 KB -- the list of flagged chunks lies in the same arrays before the
+// sort -- plus the 1 KB histogram and ~0.2 KB of scalars) and at most 128 VGPRs at 512 threads: the kernel fits beside
+// a K1 workgroup with an 84 KB row image (when the select did not, it waited for a whole CU: +8 us per configs[1]
+// step; 1,024 threads at 128 VGPRs do not fit either: step 56.0 -> 68.3 us).
 #ifndef NMZ_WT_SEL_THREADS
 #define NMZ_WT_SEL_THREADS 512
 #endif
-constexpr uint32_t WT_SEL_THREADS = NMZ_WT_SEL_THREADS;
+#ifndef NMZ_WT_SEL_KPT
+#define NMZ_WT_SEL_KPT 33
+#endif
+constexpr uint32_t WT_SEL_THREADS = NMZ_WT_SEL_THREADS, WT_SEL_KPT = NMZ_WT_SEL_KPT;
 constexpr uint32_t WT_SEL_CHUNK = 2048, WT_SEL_KEEP = (WT_CAND / WT_SEL_CHUNK) * 64;
-__global__ __launch_bounds__(WT_SEL_THREADS) void k_wt_topk_select(const uint64_t *__restrict__ sums,
-                                                                   const uint32_t *__restrict__ sorted_idx, uint64_t S,
-                                                                   uint64_t seed0, uint32_t k,
-                                                                   WtTopkState *__restrict__ tk,
+template <uint32_t CS>
+__global__ __launch_bounds__(WT_SEL_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_wt_topk_chunks(const uint32_t *__restrict__ bucket_off,
+                                                                   const WtChunkRec *__restrict__ rec,
+                                                                   const uint32_t *__restrict__ sorted_idx,
+                                                                   const nmz_sched_stats *__restrict__ stats,
+                                                                   uint64_t S, uint64_t seed0, uint32_t k,
+                                                                   uint32_t nmax, WtTopkState *__restrict__ tk,
                                                                    nmz_topk_entry *__restrict__ out) {
-    constexpr uint32_t NT = WT_SEL_THREADS, NW = NT / 64;
+    constexpr uint32_t NT = WT_SEL_THREADS, NW = NT / 64, KPT = WT_SEL_KPT;
+    static_assert(NT >= 256 && NT % 64 == 0 && CS <= 65535 && 2 * WT_SEL_CHUNK == WT_CAND, "selection layout");
     // candidates sorted in chunks of WT_SEL_CHUNK, each chunk's best k kept aside, then the kept ones sorted: 26 KB of
-    // LDS instead of 48 for one sort of WT_CAND, so the kernel fits beside a K1 workgroup whose row image has wider
-    // rank blocks (it waits for a whole CU otherwise: +8 us per configs[1] step)
+    // LDS instead of 48 for one sort of WT_CAND
     __shared__ unsigned long long ck[WT_SEL_CHUNK];
     __shared__ uint32_t ci[WT_SEL_CHUNK];
     __shared__ unsigned long long sk[WT_SEL_KEEP];
     __shared__ uint32_t si[WT_SEL_KEEP];
     __shared__ unsigned long long bk[NW], bs[NW];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t c = tk->n_cand;
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t wtot[NW], sel[2], cnt_s[2];  // cnt_s: flagged chunks, candidates
+    uint32_t *fpos = reinterpret_cast<uint32_t *>(ck);  // [WT_CAND] the flagged chunks' first positions and seed
+    uint16_t *fcnt = reinterpret_cast<uint16_t *>(ci);  // [WT_CAND] counts, until the sort takes the arrays
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
     auto sentinel = [] {
         nmz_topk_entry e;
         e.seed = UINT64_MAX;
@@ -1181,10 +1128,183 @@ __global__ __launch_bounds__(WT_SEL_THREADS) void k_wt_topk_select(const uint64_
         e.first_fault = NMZ_NONE;
         return e;
     };
+    // few instructions on a long chain of loads and barriers, beside workgroups of the neighbouring steps' sweeps
+    // that fill every issue slot: the chain's latency is what the step waits for
+    __builtin_amdgcn_s_setprio(3);
+    // the chunk keys, every load in flight together with the rows' offsets: loaded up to the records allocated
+    // (nmax >= n_chunks; a slot past n_chunks holds nothing of this sweep and is masked below)
+    unsigned long long kreg[KPT];
+#pragma unroll
+    for (uint32_t r = 0; r < KPT; ++r) {
+        const uint32_t i = tid + r * NT;
+        kreg[r] = i < nmax ? rec[i].key : 0ull;
+    }
+    const unsigned long long k0 = rec[0].key;
+    // (a) the rows' chunks
+    {
+        uint32_t v = tid < 256 ? (bucket_off[tid + 1] - bucket_off[tid] + CS - 1) / CS : 0u;
+        for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) wtot[wave] = v;
+        if (tid < 2) cnt_s[tid] = 0;
+    }
+    __syncthreads();
+    const uint32_t n = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    // (b) tau. The keys agree above bit hb, the highest bit in which any of them differs from the first. The select
+    // works on 32-bit keys, bits [sh0, sh0 + 32) of the chunk keys with sh0 = max(hb - 32, 0): all the bits that
+    // differ when hb <= 32 (sums are small), and tau is then the exact k-th largest chunk key; a wider spread leaves
+    // tau that key rounded down to a multiple of 2^sh0, still a value k chunk maxima reach. Half the registers and
+    // half the instructions of 64-bit keys: the waves run their passes one dependent instruction after another
+    const bool all = n < k;  // fewer chunks than k: tau 0, every seed a candidate
+    unsigned long long tau = 0;
+    uint32_t hb = 0;
+    if (!all) {
+        unsigned long long diff = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < KPT; ++r) diff |= tid + r * NT < n ? kreg[r] ^ k0 : 0ull;
+        for (uint32_t i = tid + KPT * NT; i < n; i += NT) diff |= rec[i].key ^ k0;
+        for (int o = 32; o; o >>= 1) diff |= __shfl_xor(diff, o, 64);
+        if (lane == 0) bk[wave] = diff;
+        __syncthreads();
+        diff = 0;
+        for (uint32_t w = 0; w < NW; ++w) diff |= bk[w];
+        hb = diff ? 64u - (uint32_t)__clzll(diff) : 0u;
+    }
+    const uint32_t sh0 = hb > 32 ? hb - 32 : 0;
+    uint32_t w32[KPT], t32 = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < KPT; ++r) w32[r] = (uint32_t)(kreg[r] >> sh0);
+    if (!all) {
+        // one digit per pass from the top: the digit's histogram over the keys that match the prefix so far, then the
+        // bin holding the kk-th largest of them. A thread adds a run of equal digits with one atomic (the first
+        // pass's keys crowd into a few bins)
+        uint32_t sh = min(hb, 32u), kk = k;
+        uint32_t pref = sh >= 32 ? 0u : ((uint32_t)(k0 >> sh0) >> sh) << sh;
+        while (sh) {
+            const uint32_t hi = sh, w = min(8u, sh);
+            sh -= w;
+            const uint32_t dm = (1u << w) - 1u;
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            uint32_t cur = 0, cnt = 0;
+            auto add = [&](uint32_t key) {
+                if (hi >= 32 || (key >> hi) == (pref >> hi)) {
+                    const uint32_t d = (key >> sh) & dm;
+                    if (d != cur && cnt) {
+                        atomicAdd(&hist[cur], cnt);
+                        cnt = 0;
+                    }
+                    cur = d;
+                    ++cnt;
+                }
+            };
+#pragma unroll
+            for (uint32_t r = 0; r < KPT; ++r)
+                if (tid + r * NT < n) add(w32[r]);
+            for (uint32_t i = tid + KPT * NT; i < n; i += NT) add((uint32_t)(rec[i].key >> sh0));
+            if (cnt) atomicAdd(&hist[cur], cnt);
+            __syncthreads();
+            // bins from the top: thread t holds bin 255 - t, an inclusive scan gives the keys at or above its bin
+            uint32_t c = 0, inc = 0;
+            if (tid < 256) {
+                c = inc = hist[255 - tid];
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t v = __shfl_up(inc, o, 64);
+                    if (lane >= (uint32_t)o) inc += v;
+                }
+                if (lane == 63) wtot[wave] = inc;
+            }
+            __syncthreads();
+            if (tid < 256) {
+                for (uint32_t x = 0; x < wave; ++x) inc += wtot[x];
+                if (inc - c < kk && kk <= inc) {  // one bin: at least kk keys match the prefix
+                    sel[0] = 255 - tid;
+                    sel[1] = kk - (inc - c);
+                }
+            }
+            __syncthreads();
+            pref |= sel[0] << sh;
+            kk = sel[1];
+        }
+        t32 = pref;
+        tau = (sh0 + 32 >= 64 ? 0ull : (k0 >> (sh0 + 32)) << (sh0 + 32)) | ((unsigned long long)pref << sh0);
+    }
+    // (c) the chunks at or above tau, listed in LDS: a thread marks its keys, then adds each marked one (~k in all)
+    {
+        static_assert(KPT <= 64, "one mark bit per register key");
+        auto list = [&](uint32_t i) {
+            const uint32_t slot = atomicAdd(&cnt_s[0], 1u);
+            if (slot < WT_CAND) {
+                fpos[slot] = rec[i].pos;
+                fcnt[slot] = (uint16_t)rec[i].cnt;
+            }
+        };
+        unsigned long long fm = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < KPT; ++r) fm |= (tid + r * NT < n && (all || w32[r] >= t32)) ? 1ull << r : 0ull;
+        while (fm) {
+            const uint32_t r = (uint32_t)__ffsll((long long)fm) - 1u;
+            fm &= fm - 1ull;
+            list(tid + r * NT);
+        }
+        for (uint32_t i = tid + KPT * NT; i < n; i += NT)
+            if (all || (uint32_t)(rec[i].key >> sh0) >= t32) list(i);
+    }
+    __syncthreads();
+    const uint32_t nf = cnt_s[0];
+    // an item per (flagged chunk, seed of it): U items per thread per round, their indices and then their sums in
+    // flight together (two dependent round trips per round; ~k flagged chunks make one round). The candidates of a
+    // single round stay in registers until the list of chunks is read, then go straight into the sort's arrays
+    constexpr uint32_t U = 16;
+    const uint32_t items = nf * CS;
+    const bool one = nf <= WT_CAND && items <= U * NT;
+    uint32_t idx[U], slot[U], fl = 0;
+    unsigned long long key[U];
+    if (nf <= WT_CAND) {
+        for (uint32_t i0 = 0; i0 < items; i0 += U * NT) {
+            bool ok[U];
+            fl = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) {
+                const uint32_t it = i0 + u * NT + tid, fi = min(it / CS, nf - 1), o = it % CS;
+                ok[u] = it < items && o < fcnt[fi];
+                idx[u] = ok[u] ? sorted_idx[fpos[fi] + o] : 0u;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) key[u] = ok[u] ? stats[idx[u]].sum_delay_ns ^ (1ull << 63) : 0ull;
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) {
+                const bool f = ok[u] && key[u] >= tau;
+                const unsigned long long mask = __ballot(f);
+                slot[u] = 0;
+                if (mask) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&cnt_s[1], (uint32_t)__popcll(mask));
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    slot[u] = base + (uint32_t)__popcll(mask & below);
+                    fl |= f ? 1u << u : 0u;
+                    if (!one && f && slot[u] < WT_CAND) {
+                        tk->cand_key[slot[u]] = key[u];
+                        tk->cand_idx[slot[u]] = idx[u];
+                    }
+                }
+            }
+        }
+        __syncthreads();  // the candidates counted (and, of several rounds, written), the list of chunks free
+    }
+    const uint32_t c = nf <= WT_CAND ? cnt_s[1] : WT_CAND + 1;
+    const bool direct = one && c <= WT_SEL_CHUNK;  // one sort chunk, filled from the registers
+    if (one && !direct && c <= WT_CAND) {
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+            if (fl >> u & 1u) {
+                tk->cand_key[slot[u]] = key[u];
+                tk->cand_idx[slot[u]] = idx[u];
+            }
+        __syncthreads();
+    }
     if (c <= WT_CAND) {
-        // every seed at or above the scan's tau is a candidate (hundreds to a few thousand: a row whose sums peak
-        // high holds many near its peak): a bitonic sort of (key desc, seed asc) in LDS, padded with key 0 (a real
-        // key has its top bit set: sums are non-negative)
+        // (d) every seed at or above tau is a candidate: a bitonic sort of (key desc, seed asc) in LDS, padded with
+        // key 0 (a real key has its top bit set: sums are non-negative)
         // bitonic sort of ck/ci[0, p2) (key desc, seed asc; padding last)
         auto sort = [&](uint32_t p2) {
             for (uint32_t kk = 2; kk <= p2; kk <<= 1)
@@ -1216,9 +1336,22 @@ __global__ __launch_bounds__(WT_SEL_THREADS) void k_wt_topk_select(const uint64_
         const uint32_t nch = c > WT_SEL_CHUNK ? (c + WT_SEL_CHUNK - 1) / WT_SEL_CHUNK : 1;
         for (uint32_t q = 0; q < nch; ++q) {
             const uint32_t lo = q * WT_SEL_CHUNK, cc = min(c - lo, WT_SEL_CHUNK), p2 = pow2(cc);
-            for (uint32_t i = threadIdx.x; i < p2; i += NT) {
-                ck[i] = i < cc ? tk->cand_key[lo + i] : 0ull;
-                ci[i] = i < cc ? (uint32_t)tk->cand_idx[lo + i] : ~0u;
+            if (direct) {
+                for (uint32_t i = cc + threadIdx.x; i < p2; i += NT) {
+                    ck[i] = 0ull;
+                    ci[i] = ~0u;
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < U; ++u)
+                    if (fl >> u & 1u) {
+                        ck[slot[u]] = key[u];
+                        ci[slot[u]] = idx[u];
+                    }
+            } else {
+                for (uint32_t i = threadIdx.x; i < p2; i += NT) {
+                    ck[i] = i < cc ? tk->cand_key[lo + i] : 0ull;
+                    ci[i] = i < cc ? tk->cand_idx[lo + i] : ~0u;
+                }
             }
             sort(p2);
             if (nch > 1) {  // the chunk's best k aside (a seed outside them is beaten by k of this chunk alone)
@@ -1250,14 +1383,15 @@ __global__ __launch_bounds__(WT_SEL_THREADS) void k_wt_topk_select(const uint64_
             }
         }
     } else {
-        // exact selection one rank at a time: the best entry after the previous one in (key desc, seed asc)
+        // (e) exact selection one rank at a time over the stats in seed order: the best entry after the previous one
+        // in (key desc, seed asc)
         unsigned long long pk = ~0ull, ps = 0;
         bool first_rank = true;
         for (uint32_t r = 0; r < k; ++r) {
             unsigned long long mk = 0, ms = ~0ull;
             bool any = false;
             for (uint64_t i = threadIdx.x; i < S; i += NT) {
-                const unsigned long long key = sums[i] ^ (1ull << 63), sd = seed0 + sorted_idx[i];
+                const unsigned long long key = stats[i].sum_delay_ns ^ (1ull << 63), sd = seed0 + i;
                 const bool after = first_rank || wt_better(pk, ps, key, sd);
                 if (after && (!any || wt_better(key, sd, mk, ms))) {
                     mk = key;
@@ -1279,7 +1413,6 @@ __global__ __launch_bounds__(WT_SEL_THREADS) void k_wt_topk_select(const uint64_
             if (lane == 0) {
                 bk[threadIdx.x >> 6] = any ? mk : 0;
                 bs[threadIdx.x >> 6] = any ? ms : ~0ull;
-                if (!any) bs[threadIdx.x >> 6] = ~0ull, bk[threadIdx.x >> 6] = 0;
             }
             __syncthreads();
             // the block's best (empty slots hold key 0, seed ~0: never better than a real entry of key 0 with a
@@ -1311,8 +1444,6 @@ __global__ __launch_bounds__(WT_SEL_THREADS) void k_wt_topk_select(const uint64_
             first_rank = false;
         }
     }
-    __syncthreads();
-    if (threadIdx.x == 0) tk->n_cand = 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1417,7 +1548,7 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
     // the widest rank blocks whose row image fits LDS (NMZ_WT_BB caps the width, A/B and tests)
     uint32_t bb = wt_max_bb();
     uint64_t off = layout(bb);
-    while (bb > 5 && std::max<uint64_t>(16, r16(off)) + 16 > WT_LDS_MAX) off = layout(--bb);
+    while (bb > 5 && std::max<uint64_t>(16, r16(off)) + 32 > WT_LDS_MAX) off = layout(--bb);
     {  // the plan kernel's dispatch order: segments by size, largest first
         std::vector<uint32_t> ord(n_cls);
         std::iota(ord.begin(), ord.end(), 0u);
@@ -1425,7 +1556,7 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
         for (uint32_t r = 0; r < n_cls; ++r) oc[r].order = ord[r];
     }
     const uint64_t rb = std::max<uint64_t>(16, r16(off));
-    if (rb + 16 > WT_LDS_MAX) return false;
+    if (rb + 32 > WT_LDS_MAX) return false;
     // function attributes are per device: once per context (a context owns one device; its calls are serialised)
     if (!ctx->wt_lds_attr) {
         for (const void *f : {reinterpret_cast<const void *>(k_replayable_sweep_wt<false, 1, 5>),
@@ -1492,37 +1623,34 @@ int wt_build(WtState &w, nmz_ctx *ctx, const uint4 *d_table, uint32_t E, const C
     return wt_launch(w, d_table, E, mod, st, nullptr, d_cls, d_rowsum, true);
 }
 
+// the candidate arrays, then one record per chunk: every row's last chunk may be partial
+static uint64_t wt_max_chunks(uint64_t S) { return S / (64 * WT_NS) + 256; }
 size_t wt_topk_scratch_bytes(uint64_t S) {
-    return Carve::bytes_for(1, sizeof(WtTopkState)) + Carve::bytes_for(S, 8);
+    return Carve::bytes_for(1, sizeof(WtTopkState)) + Carve::bytes_for(wt_max_chunks(S), sizeof(WtChunkRec));
 }
 
-// the selection after a sweep that ran with this scratch (its per-seed sums and per-workgroup largest sums)
-int wt_topk(hipStream_t st, void *scratch, const uint32_t *sorted_idx, uint64_t S, uint64_t seed0, uint32_t k,
-            nmz_topk_entry *d_out) {
+// the selection after a sweep that ran with this scratch (its chunk records) over the seeds bucketed as bucket_off
+// and sorted_idx say, with the sweep's stats
+int wt_topk(hipStream_t st, void *scratch, const uint32_t *bucket_off, const uint32_t *sorted_idx,
+            const nmz_sched_stats *d_stats, uint64_t S, uint64_t seed0, uint32_t k, nmz_topk_entry *d_out) {
     NMZ_CHECK(k >= 1 && k <= 64, "internal: wt_topk takes 1 <= k <= 64");
     Carve cv(scratch);
     WtTopkState *tk = cv.take<WtTopkState>(1);
-    const uint64_t *sums = cv.take<uint64_t>(S);
-    // (64 blocks, for less of the per-block tau derivation, made the configs[1] step slower: 0.072 -> 0.077 ms, the
-    // longer scan delaying its stream's next step)
-    const unsigned blocks = (unsigned)std::min<uint64_t>(ceil_div(S, 256), 256);
-    hipLaunchKernelGGL(k_wt_topk_scan, dim3(blocks), dim3(256), 0, st, sums, sorted_idx, S, 256 * wt_groups(), k, tk);
-    hipLaunchKernelGGL(k_wt_topk_select, dim3(1), dim3(WT_SEL_THREADS), 0, st, sums, sorted_idx, S, seed0, k, tk,
-                       d_out);
+    const WtChunkRec *rec = cv.take<WtChunkRec>(wt_max_chunks(S));
+    hipLaunchKernelGGL(k_wt_topk_chunks<64 * WT_NS>, dim3(1), dim3(WT_SEL_THREADS), 0, st, bucket_off, rec, sorted_idx,
+                       d_stats, S, seed0, k, (uint32_t)wt_max_chunks(S), tk, d_out);
     NMZ_HIP(hipGetLastError());
     return NMZ_OK;
 }
 
-// topk_scratch (wt_topk_scratch_bytes(S)) or nullptr: the sweep also leaves per-seed sums and per-workgroup largest
-// sums there for wt_topk
+// topk_scratch (wt_topk_scratch_bytes(S)) or nullptr: the sweep also leaves its chunk records there for wt_topk
 int wt_sweep(const WtState &w, nmz_ctx *ctx, hipStream_t st, const Buckets &b, const uint4 *d_table, uint32_t E,
-             const ModParams &mod, nmz_sched_stats *d_stats, uint64_t S, void *topk_scratch, uint32_t k) {
-    WtTopkState *tk = nullptr;
-    uint64_t *sums = nullptr;
+             const ModParams &mod, nmz_sched_stats *d_stats, uint64_t S, void *topk_scratch) {
+    WtChunkRec *rec = nullptr;
     if (topk_scratch) {
         Carve cv(topk_scratch);
-        tk = cv.take<WtTopkState>(1);
-        sums = cv.take<uint64_t>(S);
+        cv.take<WtTopkState>(1);
+        rec = cv.take<WtChunkRec>(wt_max_chunks(S));
     }
     const uint32_t G = wt_groups(), nt = wt_threads();
     KernelTimer kt(ctx, st, "replayable_sweep");
@@ -1530,14 +1658,14 @@ int wt_sweep(const WtState &w, nmz_ctx *ctx, hipStream_t st, const Buckets &b, c
     const bool big = mod.m32 >= 0x80000000u;
     // one seed per lane: two (NS = 2, 106 VGPRs) measured slower, K1 span 0.074 vs 0.059 ms
     // (profiles/r04/k1_ns2_rejected/)
-    auto kern = big ? (w.bb == 7 ? k_replayable_sweep_wt<true, 1, 7>
-                       : w.bb == 6 ? k_replayable_sweep_wt<true, 1, 6> : k_replayable_sweep_wt<true, 1, 5>)
-                    : (w.bb == 7 ? k_replayable_sweep_wt<false, 1, 7>
-                       : w.bb == 6 ? k_replayable_sweep_wt<false, 1, 6> : k_replayable_sweep_wt<false, 1, 5>);
-    const size_t lds = w.rb16 * 16u + 16u;
+    auto kern = big ? (w.bb == 7 ? k_replayable_sweep_wt<true, WT_NS, 7>
+                       : w.bb == 6 ? k_replayable_sweep_wt<true, WT_NS, 6> : k_replayable_sweep_wt<true, WT_NS, 5>)
+                    : (w.bb == 7 ? k_replayable_sweep_wt<false, WT_NS, 7>
+                       : w.bb == 6 ? k_replayable_sweep_wt<false, WT_NS, 6> : k_replayable_sweep_wt<false, WT_NS, 5>);
+    const size_t lds = w.rb16 * 16u + 32u;
     hipLaunchKernelGGL(kern, dim3(256 * G), dim3(nt), lds, st, b.offset, b.sorted_h0, b.sorted_idx,
                        d_table, E, w.d_blob, w.rb16, w.d_rowsum, static_cast<const WtClass *>(w.d_classes),
-                       w.n_classes, mod.m32, mod.mu, mod.m_k64, w.msh, G, d_stats, span, sums, tk, k);
+                       w.n_classes, mod.m32, mod.mu, mod.m_k64, w.msh, G, d_stats, span, rec);
     NMZ_HIP(hipGetLastError());
     return NMZ_OK;
 }
