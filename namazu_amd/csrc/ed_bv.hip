@@ -47,38 +47,13 @@
 // min(D_W, w + 1) = min(D_w, w + 1) (= min(Lev, w + 1)).
 #include <type_traits>
 
-#include "nmz_common.h"
-#include "nmz_internal.h"
+#include "ed_knn_dev.h"
+#include "ed_plan.h"
 
 namespace nmz {
 
 __device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t s) {
     return __builtin_amdgcn_alignbit(hi, lo, s);
-}
-
-__device__ __forceinline__ void bv_knn_insert(uint64_t *list, uint32_t k, uint64_t key) {
-    if (key >= __hip_atomic_load(&list[k - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    for (uint32_t s = 0; s < k; ++s) {
-        const uint64_t old = atomicMin((unsigned long long *)&list[s], (unsigned long long)key);
-        if (old == UINT64_MAX) return;
-        key = old > key ? old : key;
-    }
-}
-
-__device__ __forceinline__ void bv_knn_insert_wave(uint64_t *list, uint32_t k, uint64_t key, uint32_t lane) {
-    for (uint32_t r = 0; r < k; ++r) {
-        uint64_t best = key;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const uint64_t o = __shfl_xor(best, off, 64);
-            best = o < best ? o : best;
-        }
-        if (best == UINT64_MAX) return;
-        if (best >= __hip_atomic_load(&list[k - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-        if (lane == (uint32_t)__builtin_amdgcn_readfirstlane(__ffsll(__ballot(key == best)) - 1))
-            bv_knn_insert(list, k, best);
-        if (key == best) key = UINT64_MAX;
-    }
 }
 
 template <int W>
@@ -506,10 +481,10 @@ __device__ __forceinline__ void bv_publish(const EdBvArgs &A, bool fin, uint32_t
 #ifdef NMZ_ABL_PUBLISH
     return;  // timing only: results not listed
 #endif
-    if (b1) bv_knn_insert(A.knn + (uint64_t)j * A.k, A.k, ((uint64_t)r1 << 32) | q1);
-    if (b2) bv_knn_insert(A.knn + (uint64_t)j * A.k, A.k, ((uint64_t)r2 << 32) | q2);
-    if (__any(b1)) bv_knn_insert_wave(A.knn + (uint64_t)q1 * A.k, A.k, b1 ? (((uint64_t)r1 << 32) | j) : UINT64_MAX, lane);
-    if (__any(b2)) bv_knn_insert_wave(A.knn + (uint64_t)q2 * A.k, A.k, b2 ? (((uint64_t)r2 << 32) | j) : UINT64_MAX, lane);
+    if (b1) knn_insert(A.knn + (uint64_t)j * A.k, A.k, ((uint64_t)r1 << 32) | q1);
+    if (b2) knn_insert(A.knn + (uint64_t)j * A.k, A.k, ((uint64_t)r2 << 32) | q2);
+    if (__any(b1)) knn_insert_wave(A.knn + (uint64_t)q1 * A.k, A.k, b1 ? (((uint64_t)r1 << 32) | j) : UINT64_MAX, lane);
+    if (__any(b2)) knn_insert_wave(A.knn + (uint64_t)q2 * A.k, A.k, b2 ? (((uint64_t)r2 << 32) | j) : UINT64_MAX, lane);
 }
 
 __device__ __forceinline__ void bv_load_block(uint32_t (&dst)[16], const uint16_t *stream, uint32_t blk) {
@@ -522,7 +497,7 @@ __device__ __forceinline__ void bv_load_block(uint32_t (&dst)[16], const uint16_
 }
 
 // ---------------------------------------------------------------------------
-// q-gram filter (nmz_internal.h ED_QG_*): bucket of the adjacent pair (x, y) of stream values (Peq-row byte
+// q-gram filter (ed_plan.h ED_QG_*): bucket of the adjacent pair (x, y) of stream values (Peq-row byte
 // offsets, i.e. dense symbol ids; 0xffff for a query symbol the store lacks, which merges such symbols -- a
 // valid coarsening). Profiles are built once per plan; a lane compares its candidate's profile with the
 // workgroup's query profiles by v_sad_u8 (|a - b| summed over 4 packed counts) before any DP.
@@ -854,15 +829,15 @@ __global__ __launch_bounds__(256) NMZ_ED_BV_ATTR void k_ed_bv(EdBvArgs A) {
             bool a1 = dd1 <= w && dd1 >= -w, a2 = vv2 && dd2 <= w && dd2 >= -w;
             if (a1 && (n1 == 0 || mm[u] == 0)) {
                 const uint64_t r = n1 + mm[u];
-                bv_knn_insert(A.knn + (uint64_t)jj * A.k, A.k, (r << 32) | q1);
-                bv_knn_insert(A.knn + (uint64_t)q1 * A.k, A.k, (r << 32) | jj);
+                knn_insert(A.knn + (uint64_t)jj * A.k, A.k, (r << 32) | q1);
+                knn_insert(A.knn + (uint64_t)q1 * A.k, A.k, (r << 32) | jj);
                 c_in_band += 1;
                 a1 = false;
             }
             if (a2 && (n2 == 0 || mm[u] == 0)) {
                 const uint64_t r = n2 + mm[u];
-                bv_knn_insert(A.knn + (uint64_t)jj * A.k, A.k, (r << 32) | q2);
-                bv_knn_insert(A.knn + (uint64_t)q2 * A.k, A.k, (r << 32) | jj);
+                knn_insert(A.knn + (uint64_t)jj * A.k, A.k, (r << 32) | q2);
+                knn_insert(A.knn + (uint64_t)q2 * A.k, A.k, (r << 32) | jj);
                 c_in_band += 1;
                 a2 = false;
             }
@@ -899,7 +874,7 @@ __global__ __launch_bounds__(256) NMZ_ED_BV_ATTR void k_ed_bv(EdBvArgs A) {
 }
 
 // ---------------------------------------------------------------------------
-// Two-phase search (nmz_internal.h EdQgArgs): filter tiles, then DP work items.
+// Two-phase search (ed_plan.h EdQgArgs): filter tiles, then DP work items.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t qg_l1_reg(const uint4 (&c)[ED_QG_DW / 4], const uint4 *q) {
     uint32_t s = 0;
@@ -915,7 +890,7 @@ __device__ __forceinline__ uint32_t qg_l1_reg(const uint4 (&c)[ED_QG_DW / 4], co
 }
 
 // One tile: queries [64 qb, 64 qb + 64) x candidates [256 cb, 256 cb + 256), pairs j > q only (the shard's tile
-// list: csrc/ed.hip ed_bv_two_phase).
+// list: csrc/ed_tp.hip ed_bv_two_phase).
 // the tile of hardware block b: XCD b % 8 takes a contiguous eighth of the list (its superblocks' profiles stay in
 // that XCD's L2); the grid is a multiple of 8
 __device__ __forceinline__ uint64_t qg_tile_of_block() {
@@ -961,8 +936,8 @@ __global__ __launch_bounds__(256) void k_ed_qg_filter(EdQgArgs A) {
             if (a1 && (n1 == 0 || m == 0)) {  // an empty trace: n + m <= w, listed once (count pass)
                 if (COUNT) {
                     const uint64_t r = n1 + m;
-                    bv_knn_insert(A.knn + (uint64_t)j * A.k, A.k, (r << 32) | q1);
-                    bv_knn_insert(A.knn + (uint64_t)q1 * A.k, A.k, (r << 32) | j);
+                    knn_insert(A.knn + (uint64_t)j * A.k, A.k, (r << 32) | q1);
+                    knn_insert(A.knn + (uint64_t)q1 * A.k, A.k, (r << 32) | j);
                     c_in_band += 1;
                 }
                 a1 = false;
@@ -970,8 +945,8 @@ __global__ __launch_bounds__(256) void k_ed_qg_filter(EdQgArgs A) {
             if (a2 && (n2 == 0 || m == 0)) {
                 if (COUNT) {
                     const uint64_t r = n2 + m;
-                    bv_knn_insert(A.knn + (uint64_t)j * A.k, A.k, (r << 32) | q2);
-                    bv_knn_insert(A.knn + (uint64_t)q2 * A.k, A.k, (r << 32) | j);
+                    knn_insert(A.knn + (uint64_t)j * A.k, A.k, (r << 32) | q2);
+                    knn_insert(A.knn + (uint64_t)q2 * A.k, A.k, (r << 32) | j);
                     c_in_band += 1;
                 }
                 a2 = false;
@@ -1212,8 +1187,8 @@ __global__ __launch_bounds__(256) void k_ed_bv_query(EdBvQueryArgs A) {
     bool need = true, first = true;
     auto publish = [&](bool fin) {  // in-band results only (k_knn_fill completes the lists, as in k_ed_bv)
         const bool b1 = fin && r1 <= w, b2 = fin && has2 && r2 <= w;
-        if (__any(b1)) bv_knn_insert_wave(A.knn, A.k, b1 ? (((uint64_t)r1 << 32) | j) : UINT64_MAX, lane);
-        if (__any(b2)) bv_knn_insert_wave(A.knn + A.k, A.k, b2 ? (((uint64_t)r2 << 32) | j) : UINT64_MAX, lane);
+        if (__any(b1)) knn_insert_wave(A.knn, A.k, b1 ? (((uint64_t)r1 << 32) | j) : UINT64_MAX, lane);
+        if (__any(b2)) knn_insert_wave(A.knn + A.k, A.k, b2 ? (((uint64_t)r2 << 32) | j) : UINT64_MAX, lane);
     };
     while (true) {
         while (true) {

@@ -18,8 +18,8 @@
 // ~55 VALU instructions per column cover 2w+1 = 8193 DP cells.
 // Bands 64 < w <= 8192 run on the kernel of the smallest W = 1024 * 2^k >= w with w applied at run time
 // (length band, cut-off, clamp; exact as in ed_bv.hip: min(D_W, w + 1) = min(D_w, w + 1)).
-#include "nmz_common.h"
-#include "nmz_internal.h"
+#include "ed_knn_dev.h"
+#include "ed_plan.h"
 
 namespace nmz {
 
@@ -33,15 +33,6 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
     return __builtin_amdgcn_readfirstlane(v);  // uniform: keeps dependent control flow scalar
-}
-
-__device__ __forceinline__ void wide_knn_insert(uint64_t *list, uint32_t k, uint64_t key) {
-    if (key >= __hip_atomic_load(&list[k - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    for (uint32_t s = 0; s < k; ++s) {
-        const uint64_t old = atomicMin((unsigned long long *)&list[s], (unsigned long long)key);
-        if (old == UINT64_MAX) return;
-        key = old > key ? old : key;
-    }
 }
 
 template <int KL>
@@ -228,8 +219,8 @@ __global__ __launch_bounds__(256) void k_ed_wide(EdWideArgs A) {
     const uint32_t m = __builtin_amdgcn_readfirstlane((uint32_t)(A.off[j + 1] - A.off[j]));
     const uint32_t r = wide_pair<KL>(A, A.peq + (uint64_t)i * A.n_sym * A.ndw, n, j, m, lane);
     if (lane == 0) {
-        wide_knn_insert(A.knn + i * A.k, A.k, ((uint64_t)r << 32) | j);
-        wide_knn_insert(A.knn + j * A.k, A.k, ((uint64_t)r << 32) | i);
+        knn_insert(A.knn + i * A.k, A.k, ((uint64_t)r << 32) | j);
+        knn_insert(A.knn + j * A.k, A.k, ((uint64_t)r << 32) | i);
     }
 }
 
@@ -251,7 +242,7 @@ __global__ __launch_bounds__(256) void k_ed_wide_query(EdWideArgs A, const uint3
     const uint32_t n = __builtin_amdgcn_readfirstlane(qlen[q]);
     const uint32_t m = __builtin_amdgcn_readfirstlane((uint32_t)(A.off[j + 1] - A.off[j]));
     const uint32_t r = wide_pair<KL>(A, qpeq + (uint64_t)q * qstride, n, j, m, lane);
-    if (lane == 0 && r <= A.w) wide_knn_insert(A.knn + (uint64_t)q * A.k, A.k, ((uint64_t)r << 32) | j);
+    if (lane == 0 && r <= A.w) knn_insert(A.knn + (uint64_t)q * A.k, A.k, ((uint64_t)r << 32) | j);
 }
 
 // match bitmaps: peq[i][c][dword], bit (pos + 1 + OFF) of row sym[pos] for every position of trace i

@@ -38,7 +38,7 @@
 #include <utility>
 
 #include "nmz_common.h"
-#include "nmz_internal.h"
+#include "ed_plan.h"
 
 namespace nmz {
 

@@ -342,7 +342,7 @@ int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_
     return NMZ_OK;
 }
 
-// Sorted distinct values of d_sym[0..total) (the bit-parallel ED plan's alphabet, ed.hip). A store holds
+// Sorted distinct values of d_sym[0..total) (the bit-parallel ED plan's alphabet, ed_build.hip). A store holds
 // ~10^8 event hashes over at most a few thousand distinct events, so the distinct set comes from hashing, not
 // from sorting the store: each workgroup dedups its grid-stride share in an LDS open-addressing table (a plain
 // read finds a present key, a 64-bit LDS compare-and-swap claims a free slot) and then inserts its distinct keys

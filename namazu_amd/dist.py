@@ -28,7 +28,7 @@ def shard_range(total, world, rank):
 
 def ed_block_shard(qb, world):
     """Shard owning query block qb (queries 64 qb .. 64 qb + 63) of the two-phase all-pairs search
-    (nmz_ed_allpairs_knn_shard_dev; csrc/ed.hip ed_block_shard): in each period of 2 world blocks, block r and
+    (nmz_ed_allpairs_knn_shard_dev; csrc/ed_plan.h ed_block_shard): in each period of 2 world blocks, block r and
     its mirror 2 world - 1 - r form a pair (the falling work per block inside the upper triangle and inside each
     family of near-duplicates cancels between them), and pair p of period g goes to shard (p + g) mod world, so
     every shard takes every position. Whole query blocks, so a query pair's DP entries stay in one shard. A fixed

@@ -456,16 +456,21 @@ def test_search_similar_on_storage_uses_resident_index(ctx, tmp_path):
 def test_device_and_host_plan_builds_agree(ab_knobs, ctx, monkeypatch):
     """Stores of >= 2^20 symbols build the bit-parallel plan on the device (sort/unique + binary-search remap);
     NMZ_ED_HOST_REMAP forces the host build. Both give the oracle's k-NN lists and the same single-query answers
-    (the query dictionary comes from the device's sorted symbols)."""
+    (the query dictionary comes from the device's sorted symbols), and plans with the same fingerprint (both builders
+    take the plan's shape from one function, csrc/ed_build.hip bv_plan_shape)."""
     rng = np.random.default_rng(77)
     ts = make_traces(600, 1700, 2000, 0.01, alphabet=40, rng=rng)
     assert int(ts.off[-1]) >= 1 << 20
+    fp_d = _plan_fp(ctx, ts, 32)
     ids_d, ds_d = knn(ctx, ts, 32, 5)
     qs = [ts.trace(5), ts.trace(9)[:1500]]
     qi_d, qd_d = hs.SimilarityIndex(ts, 32, ctx=ctx).query(qs, 4)
     monkeypatch.setenv("NMZ_ED_HOST_REMAP", "1")
     ids_h, ds_h = knn(ctx, ts, 32, 5)
     qi_h, qd_h = hs.SimilarityIndex(ts, 32, ctx=ctx).query(qs, 4)
+    fp_h = _plan_fp(ctx, ts, 32)
+    print("fingerprints device/host:", fp_d.tolist(), fp_h.tolist())
+    assert np.array_equal(fp_d, fp_h)
     assert np.array_equal(ids_d, ids_h) and np.array_equal(ds_d, ds_h)
     assert np.array_equal(qi_d, qi_h) and np.array_equal(qd_d, qd_h)
     for q in [0, 299, 599]:
@@ -503,13 +508,17 @@ def test_device_plan_symbols_zero_and_all_ones(ab_knobs, ctx, monkeypatch):
 def test_wide_device_and_host_plan_builds_agree(ab_knobs, ctx, monkeypatch):
     """Wide-band stores of >= 2^20 symbols build k_ed_wide's plan on the device (hash-set alphabet + remap kernel,
     ids by sorted rank instead of first appearance); NMZ_ED_HOST_REMAP forces the host build. Same k-NN lists,
-    and the oracle's for sampled queries."""
+    the same plan fingerprint, and the oracle's lists for sampled queries."""
     rng = np.random.default_rng(80)
     ts = make_traces(300, 3600, 3900, 0.02, alphabet=40, rng=rng)
     assert int(ts.off[-1]) >= 1 << 20
+    fp_d = _plan_fp(ctx, ts, 1500)
     ids_d, ds_d = knn(ctx, ts, 1500, 4)
     monkeypatch.setenv("NMZ_ED_HOST_REMAP", "1")
     ids_h, ds_h = knn(ctx, ts, 1500, 4)
+    fp_h = _plan_fp(ctx, ts, 1500)
+    print("fingerprints device/host:", fp_d.tolist(), fp_h.tolist())
+    assert np.array_equal(fp_d, fp_h)
     assert np.array_equal(ids_d, ids_h) and np.array_equal(ds_d, ds_h)
     for q in [0, 157]:
         pairs = np.array([[q, c] for c in range(len(ts)) if c != q], np.uint32)
@@ -616,7 +625,7 @@ def test_knn_qgram_filter_exact(ab_knobs, ctx, monkeypatch, w, alphabet, max_edi
 @pytest.mark.parametrize("limit", [0, 1, 500, "mid"])
 def test_knn_two_phase_entry_limit_batches(ab_knobs, ctx, monkeypatch, limit):
     """Entry lists beyond the two-phase limit (2^30 entries; NMZ_ED_TP_MAX_ENTRIES lowers it) run in batches of
-    whole query blocks after the count pass (csrc/ed.hip ed_bv_two_phase). The count pass lists pairs with an empty
+    whole query blocks after the count pass (csrc/ed_tp.hip ed_bv_two_phase). The count pass lists pairs with an empty
     trace before the total is known, so the batches must start from empty lists: near-duplicates with empty traces
     in the store (n + m <= w pairs), vs the oracle, through the one-shard and the 3-shard (merge + fill) paths.
     "mid" puts the limit between the shards' own entry totals, so some shards of one search split into batches and
@@ -747,6 +756,16 @@ def test_knn_compact_tables_forced(ab_knobs, ctx, monkeypatch, w):
 def _fp(L, plan):
     fp = np.zeros(_lib.NMZ_ED_FP_WORDS, np.uint64)
     _lib.check(L.nmz_ed_plan_fingerprint(plan, _lib.ptr(fp)))
+    return fp
+
+
+def _plan_fp(ctx, ts, w):
+    """nmz_ed_plan_fingerprint's words of the plan nmz_ed_plan_create builds under the current environment."""
+    L = _lib.load()
+    plan = ctypes.c_void_p()
+    _lib.check(L.nmz_ed_plan_create(ctx.handle, _lib.ptr(ts.off), _lib.ptr(ts.sym), len(ts), w, ctypes.byref(plan)))
+    fp = _fp(L, plan)
+    L.nmz_ed_plan_destroy(plan)
     return fp
 
 
@@ -898,7 +917,7 @@ def test_two_phase_offset_kernels(ctx, n, item, big):
 
 
 def test_cached_searches_back_to_back_then_destroy(ctx):
-    """Cached searches publish their mismatch flag from the offsets scan into pinned host words (csrc/ed.hip
+    """Cached searches publish their mismatch flag from the offsets scan into pinned host words (csrc/ed_tp.hip
     ed_tp_flag_*: a sequence number, then the flag; no copy or event on the queue). Enqueued back to back without a
     synchronisation, none reports a mismatch (a number not yet landed is read later) and the last one's lists equal
     the oracle; destroying the plan right after a burst waits for the last scan's words before freeing them."""
@@ -939,7 +958,7 @@ def test_cached_searches_back_to_back_then_destroy(ctx):
 
 
 def test_cached_size_mismatch_skips_writes_and_surfaces(ab_knobs, ctx, monkeypatch):
-    """A shard's later searches run with the sizes its first search read back (csrc/ed.hip ed_bv_two_phase); a
+    """A shard's later searches run with the sizes its first search read back (csrc/ed_tp.hip ed_bv_two_phase); a
     one-thread check flags a search whose own totals differ. NMZ_ED_TP_FAKE_MISMATCH forces the flag on a cached
     search: that search writes no entry and runs no DP (nothing past the lists sized for the cached totals), the
     shard's next search reports it (NMZ_EHIP) and drops the cache, and the search after that is whole again and
