@@ -245,6 +245,13 @@ int nmz_replayable_plan_destroy(nmz_replayable_plan *plan);
  * 1 = order-query statistics (k_replayable_sweep_oq), 0 = per-decision sweeps; -1 for a NULL plan. The environment
  * variable NMZ_REPLAY_WT=0 at plan creation skips the wavelet trees (A/B runs). */
 int nmz_replayable_plan_kernel(const nmz_replayable_plan *plan);
+/* The form of a wavelet-tree plan (diagnostic; an error for a plan whose sweeps take another kernel): *bb = log2 of
+ * the rank blocks' width (5, 6 or 7), *planes = 1 when the segments hold rank-block planes in place of the levels
+ * above the blocks (64-rank blocks and a row image of at most 128 KB; NMZ_WT_PLANES=0 at plan creation keeps the
+ * levels, A/B runs), *image_bytes = the bytes of one row image (staged into LDS per sweep workgroup). Any of the three
+ * may be NULL. */
+int nmz_replayable_plan_wt_info(const nmz_replayable_plan *plan, uint32_t *bb, uint32_t *planes,
+                                uint64_t *image_bytes);
 int nmz_replayable_sweep_dev(nmz_replayable_plan *plan, const uint32_t *d_seed_off,
                              const uint8_t *d_seed_bytes, uint64_t n_seeds,
                              nmz_sched_stats *d_stats, void *stream);

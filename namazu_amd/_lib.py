@@ -119,6 +119,7 @@ SIGNATURES = {
     "nmz_replayable_sweep_traces": (_int, [_P, _u32, _P, _P, _P, _i64, _u64, _u64, _u32, _P]),
     "nmz_replayable_plan_destroy": (_int, [_P]),
     "nmz_replayable_plan_kernel": (_int, [_P]),
+    "nmz_replayable_plan_wt_info": (_int, [_P, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
     "nmz_replayable_sweep_dev": (_int, [_P, _P, _P, _u64, _P, _P]),
     "nmz_replayable_sweep_topk_dev": (_int, [_P, _P, _P, _u64, _u64, _u32, _P, _P, _P]),
     "nmz_replayable_order_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _u32, _P, _P]),

@@ -580,6 +580,16 @@ int nmz_replayable_plan_kernel(const nmz_replayable_plan *plan) {
     return plan->wt.on ? 2 : plan->oq.on ? 1 : 0;
 }
 
+int nmz_replayable_plan_wt_info(const nmz_replayable_plan *plan, uint32_t *bb, uint32_t *planes,
+                                uint64_t *image_bytes) {
+    NMZ_CHECK(plan != nullptr, "plan is NULL");
+    NMZ_CHECK(plan->wt.on, "the plan does not run the wavelet-tree kernel");
+    if (bb) *bb = plan->wt.bb;
+    if (planes) *planes = plan->wt.planes ? 1u : 0u;
+    if (image_bytes) *image_bytes = (uint64_t)plan->wt.rb16 * 16u;
+    return NMZ_OK;
+}
+
 int nmz_replayable_sweep_dev(nmz_replayable_plan *plan, const uint32_t *d_seed_off, const uint8_t *d_seed_bytes,
                              uint64_t n_seeds, nmz_sched_stats *d_stats, void *stream) {
     NMZ_CHECK(plan != nullptr, "plan is NULL");

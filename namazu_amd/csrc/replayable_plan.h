@@ -90,6 +90,7 @@ struct WtState {
     bool on = false;
     uint32_t rb16 = 0, n_classes = 0, msh = 0;
     uint32_t bb = 5;                        // rank blocks of 2^bb ranks below the tree's levels (replayable_wt.hip)
+    bool planes = false;                    // rank-block planes instead of levels (bb = 6, every segment or none)
     uint4 *d_blob = nullptr;                // [256][rb16] row images
     unsigned long long *d_rowsum = nullptr;  // [256] sum of C mod m over the row
     void *d_classes = nullptr;              // [n_classes] segment descriptors
@@ -109,7 +110,8 @@ struct WtClass {
     uint32_t o_mk;            //   block masks [(n >> bb) + 1][2^bb + 1] of 2^bb bits: the ranks (bit r mod 2^bb)
                               //   among the first o entries of each 2^bb-rank block's node, o = 0..2^bb
     uint32_t order;           // plan kernel: the segment whose rows the order-th group of 256 workgroups builds
-    uint32_t pad;
+    uint32_t o_pl;            //   rank-block planes [(n >> 6) + 2][nw] {bits, ones before} in place of the levels
+                              //   (plane b: rank >= 64 b, in position order), or 0: the segment has levels
 };
 static_assert(sizeof(WtClass) == 64, "WtClass layout");
 

@@ -14,6 +14,9 @@
 // where the predecessor of R inside the part branches off, from which a short second descent reaches it.
 // Ranks sort by (Cm ascending, e descending), so among equal Cm the highest rank is the first event: the
 // predecessor's event is the reference's first-index argmax (the order of its `>` test).
+// A plan whose row image stays small enough (configs[1]'s) stores, instead of the levels, one plane per boundary
+// between 64-rank blocks: the count is then two plane reads and a mask, the predecessor a search over blocks
+// (wt_plane_bytes, the PL form of wt_seed_class).
 //
 // Per (seed, segment of n ~ 2,000 events): ~3 lifting searches of ~5 LDS reads (d over C's high words,
 // R_A and R_B over the sorted Cm through 256-bucket indexes), 2 x ceil(log2 n + 1) descent reads, a few
@@ -70,6 +73,19 @@ __host__ __device__ constexpr uint32_t wt_levels(uint32_t K, uint32_t bb) { retu
 __host__ __device__ constexpr uint64_t wt_mask_bytes(uint32_t n, uint32_t bb) {
     return (uint64_t)((n >> bb) + 1) * ((1u << bb) + 1) * ((1u << bb) / 8);
 }
+
+// Rank-block planes (64-rank blocks only) replace the levels of a plan whose row image stays small enough: with
+// NB = (n >> 6) + 1 blocks, plane b (b = 0 .. NB) holds bit i = [rank_i >= 64 b] in position order, stored like a
+// level, so f_b(d) = #{i < d: rank_i >= 64 b} is one read and a count needs two dependent rounds (two planes, one
+// mask) instead of a descent of K - 6 levels. Plane bytes grow as n^2 / 256 (16.6 KB for 2,079 events against 3.1 KB
+// of levels; 65 KB for 4,095).
+__host__ __device__ constexpr uint64_t wt_plane_bytes(uint32_t n, uint32_t nw) {
+    return (uint64_t)((n >> 6) + 2) * nw * 8;
+}
+// One K1 workgroup's row image and the 26.7 KB of static LDS of k_wt_topk_chunks must fit a CU's 160 KB together, or
+// the selection of the neighbouring step waits for a whole CU (the 118 KB images of 128-rank blocks cost the
+// pipelined step that overlap): planes are taken only while the row image is at most 128 KB.
+constexpr uint64_t WT_PLANES_MAX = 128 * 1024;
 
 // A block's prefix mask (2^BB bits) and the few operations the descents need on it
 template <int BB>
@@ -467,6 +483,59 @@ __global__ __launch_bounds__(WT_BT) void k_replayable_wt_build(const uint4 *__re
 #endif
     WT_STAMP(5);
     WT_STAMP(6);
+    if constexpr (BB == 6) {
+        if (ci.o_pl) {
+            // rank-block planes instead of levels (wt_layout): plane b = [rank >= 64 b] in position order, b = 0 .. nbk
+            // (plane 0 all ones, plane nbk all zeros: the sweep reads f_b(d) for every b it can form without a select),
+            // one {32 bits, ones before} pair per 32 positions like a level. A wave takes every WT_BW-th plane and
+            // walks the 64-position groups in order (ballot, running count); the same walk lists block b's ranks in
+            // position order -- the node the level passes would have ended with -- for the block's prefix masks.
+            const uint32_t nbk = (n >> 6) + 1, nw = ci.nw, ng = (nw + 1) / 2;
+            uint2 *pl = reinterpret_cast<uint2 *>(img + ci.o_pl);
+            uint64_t *mk = reinterpret_cast<uint64_t *>(img + ci.o_mk);
+            uint8_t *ord = reinterpret_cast<uint8_t *>(bc) + 64 * wave;  // [64] the block's ranks mod 64 (bc is free)
+            const uint64_t below = (1ull << lane) - 1ull;
+            for (uint32_t b = wave; b <= nbk; b += WT_BW) {
+                uint32_t pre = 0, inb = 0, wlo = 0, whi = 0, wpre = 0;  // lane g keeps group g's two words (ng <= 64)
+#pragma unroll 4
+                for (uint32_t g = 0; g < ng; ++g) {
+                    const uint32_t j = g * 64 + lane, v = j < n ? S0[j] : 0u;
+                    const uint64_t bg = __ballot(j < n && (v >> 6) >= b), be = __ballot(j < n && (v >> 6) == b);
+                    if (lane == g) {
+                        wlo = (uint32_t)bg;
+                        whi = (uint32_t)(bg >> 32);
+                        wpre = pre;
+                    }
+                    if (be >> lane & 1) ord[inb + (uint32_t)__popcll(be & below)] = (uint8_t)(v & 63);
+                    pre += (uint32_t)__popcll(bg);
+                    inb += (uint32_t)__popcll(be);
+                }
+                if (lane < ng) {
+                    pl[b * nw + 2 * lane] = make_uint2(wlo, wpre);
+                    if (2 * lane + 1 < nw) pl[b * nw + 2 * lane + 1] = make_uint2(whi, wpre + (uint32_t)__popc(wlo));
+                }
+                if (b < nbk) {  // entry o of block b = the OR of bit (rank mod 64) over the block's first o entries
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    unsigned long long v = lane < inb ? 1ull << ord[lane] : 0ull;
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const unsigned long long u = __shfl_up(v, o, 64);
+                        if (lane >= (uint32_t)o) v |= u;
+                    }
+                    mk[b * 65 + lane + 1] = v;
+                    if (lane == 0) mk[b * 65] = 0;
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+            WT_STAMP(7);
+#ifdef WT_BUILD_TRACE
+            __syncthreads();
+#endif
+            WT_STAMP(8);
+            return;
+        }
+    }
     // wavelet levels above the 32-rank blocks. Per level, wave w ballots a contiguous range of 64-position groups
     // (bit K-1-l of the rank at each position, in this level's order), the 8 wave totals give each wave its ones
     // before its range, and every position's destination in the next level's order follows from the ones before it
@@ -631,7 +700,8 @@ struct WtVConst {
 // NS seeds per lane (arrays indexed by u, unrolled): the wave-uniform control -- segment parameters, lifting
 // rounds, level constants, loop trips, ballots -- is paid once for NS seeds, and the NS seeds' read chains are
 // independent, so a wave keeps 2 NS dependent LDS chains in flight per descent level instead of 2.
-template <bool BIG, int NS, int BB>
+// PL (BB = 6 only): the plan's segments hold rank-block planes instead of levels.
+template <bool BIG, int NS, int BB, bool PL>
 __device__ __forceinline__ void wt_seed_class(const WtVConst &vc, const WtClass &ci, const char *__restrict__ img,
                                               const uint4 *__restrict__ row, const uint64_t (&h0)[NS], uint32_t m,
                                               uint64_t mu, uint32_t m_k64, uint32_t msh, uint64_t (&sum)[NS],
@@ -722,14 +792,104 @@ __device__ __forceinline__ void wt_seed_class(const WtVConst &vc, const WtClass 
             while (d[u] < n && chi[d[u]] == nh[u] && row[ci.start + d[u]].x <= nl) ++d[u];
         }
     }
-    // descents along R_A's and R_B's paths with the prefix [0, d) down to R's 32-rank block, branch-free with every
-    // read of a level in flight: counts of ranks >= R, and the deepest level where a part's elements below R branch
-    // off (the predecessor's subtree: node start s, prefix offset q)
-    const uint2 *__restrict__ lv = reinterpret_cast<const uint2 *>(img + ci.o_lv);
     const char *__restrict__ mk = img + ci.o_mk;
     using MK = WtMask<BB>;
     using MT = typename MK::T;
     constexpr uint32_t BW = 1u << BB, BM = BW - 1;
+    // each part's maximum: the rank pA / pB of its predecessor of R, or of its largest element when it wraps
+    uint32_t pA[NS], pB[NS];
+    bool wrapA[NS], wrapB[NS];
+    if constexpr (PL) {
+        // Planes: f_b(d) = #{i < d: rank_i >= 64 b} is one read of plane b (b = 0 .. NB, NB = (n >> 6) + 1), so with
+        // b = R >> 6 the prefix part has o = f_b(d) - f_{b+1}(d) elements in R's block -- the index of the block's
+        // prefix mask -- and f_{b+1}(d) + count_ge(mask, R & 63) ranks >= R: two dependent rounds for both counts.
+        static_assert(!PL || BB == 6, "planes stand on 64-rank blocks");
+        const uint32_t NB = (n >> 6) + 1;
+        const uint32_t nv = wt_v(n), nw8 = wt_v(ci.nw * 8u), nbv = wt_v(NB), six = wt_v(6u);
+        const char *pd[NS];  // the word of position d in plane 0; plane b's is nw8 * b bytes on
+        auto fcount = [](const char *q, uint32_t dd) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(q);
+            return w.y + __popc(__builtin_amdgcn_ubfe(w.x, 0u, dd));
+        };
+        uint32_t bA[NS], bB[NS], fA0[NS], fB0[NS], cA[NS], cB[NS];
+        MT belA[NS], belB[NS];
+        bool hitA[NS], hitB[NS];
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+            pd[u] = img + ci.o_pl + (d[u] >> 5) * 8u;
+            bA[u] = RA[u] >> six;
+            bB[u] = RB[u] >> six;
+            const char *qa = pd[u] + bA[u] * nw8, *qb = pd[u] + bB[u] * nw8;
+            fA0[u] = fcount(qa, d[u]);
+            fB0[u] = fcount(qb, d[u]);
+            const uint32_t fA1 = fcount(qa + nw8, d[u]), fB1 = fcount(qb + nw8, d[u]);
+            const uint32_t rA = RA[u] & BM, rB = RB[u] & BM;
+            const MT mA = MK::load(mk, (RA[u] & ~BM) + bA[u] + (fA0[u] - fA1));
+            const MT mB = MK::load(mk, (RB[u] & ~BM) + bB[u] + (fB0[u] - fB1));
+            cA[u] = fA1 + MK::count_ge(mA, rA);
+            cB[u] = fB1 + MK::count_ge(mB, rB);
+            W[u] += cA[u] + (n - RB[u]) - cB[u];
+            belA[u] = MK::below(mA, rA);
+            belB[u] = MK::below(MK::inv(mB), rB);
+            hitA[u] = MK::any(belA[u]);
+            hitB[u] = MK::any(belB[u]);
+        }
+        // predecessors outside R's block: a search over blocks. The suffix part's counts are
+        // g_b(d) = #{i >= d: rank_i >= 64 b} = n - 64 b - f_b(d) (negative only at b = NB: compared signed). A part
+        // with elements below R (d - cA of the prefix, R_B - (d - cB) of the suffix) takes the largest block of
+        // [0, b - 1] whose count exceeds block b's; a part with none wraps and takes the largest block of [b, NB - 1]
+        // with any element. Counts do not increase with b: one lifting search from the range's first block, reads
+        // clamped to plane NB (all zeros); steps longer than every lane's range are skipped.
+        constexpr uint32_t OFF = 0x7fffffffu;  // no count exceeds it: the lanes that search nothing stay at block 0
+        uint32_t posA[NS], posB[NS], TA[NS], TB[NS], rng = 0;
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+            const bool dA = d[u] > 0 && !hitA[u], dB = d[u] < n && !hitB[u];
+            wrapA[u] = dA && d[u] == cA[u];
+            wrapB[u] = dB && RB[u] + cB[u] == d[u];
+            posA[u] = wrapA[u] ? bA[u] : 0u;
+            posB[u] = wrapB[u] ? bB[u] : 0u;
+            TA[u] = !dA ? OFF : wrapA[u] ? 0u : fA0[u];
+            TB[u] = !dB ? OFF : wrapB[u] ? 0u : nv - (bB[u] << six) - fB0[u];
+            const uint32_t rA = !dA ? 0u : wrapA[u] ? nbv - 1u - bA[u] : bA[u] - 1u;
+            const uint32_t rB = !dB ? 0u : wrapB[u] ? nbv - 1u - bB[u] : bB[u] - 1u;
+            rng = max(rng, max(rA, rB));
+        }
+#ifdef WT_ABL_PRED
+        if (0)
+#endif
+        if (__builtin_amdgcn_ballot_w64(rng != 0)) {
+#pragma unroll
+            for (uint32_t st = 32; st; st >>= 1) {
+                if (st >= NB || !__builtin_amdgcn_ballot_w64(rng >= st)) continue;
+                const uint32_t stv = wt_v(st);
+#pragma unroll
+                for (int u = 0; u < NS; ++u) {
+                    const uint32_t qa = min(posA[u] + stv, nbv), qb = min(posB[u] + stv, nbv);
+                    const uint32_t fa = fcount(pd[u] + qa * nw8, d[u]), fb = fcount(pd[u] + qb * nw8, d[u]);
+                    posA[u] = (int32_t)fa > (int32_t)TA[u] ? qa : posA[u];
+                    posB[u] = (int32_t)(nv - (qb << six) - fb) > (int32_t)TB[u] ? qb : posB[u];
+                }
+            }
+        }
+        // the found block's prefix count, then its mask: the prefix part's largest rank there, or the suffix part's
+        // (the inverted mask cut to the block's min(n - 64 pos, 64) ranks)
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+            const char *qa = pd[u] + posA[u] * nw8, *qb = pd[u] + posB[u] * nw8;
+            const uint32_t oa = fcount(qa, d[u]) - fcount(qa + nw8, d[u]);
+            const uint32_t ob = fcount(qb, d[u]) - fcount(qb + nw8, d[u]);
+            const uint32_t sa = posA[u] << six, sb = posB[u] << six;
+            const MT vA = MK::load(mk, sa + posA[u] + oa);
+            const MT vB = MK::low(MK::inv(MK::load(mk, sb + posB[u] + ob)), min(nv - sb, BW));
+            pA[u] = hitA[u] ? (RA[u] & ~BM) + MK::top(belA[u]) : sa + MK::top(vA);
+            pB[u] = hitB[u] ? (RB[u] & ~BM) + MK::top(belB[u]) : sb + MK::top(vB);
+        }
+    } else {
+    // descents along R_A's and R_B's paths with the prefix [0, d) down to R's 32-rank block, branch-free with every
+    // read of a level in flight: counts of ranks >= R, and the deepest level where a part's elements below R branch
+    // off (the predecessor's subtree: node start s, prefix offset q)
+    const uint2 *__restrict__ lv = reinterpret_cast<const uint2 *>(img + ci.o_lv);
 #ifdef WT_ABL_COUNT
     const uint32_t K = ci.K, nw = ci.nw, lb = 0;
 #else
@@ -794,7 +954,7 @@ __device__ __forceinline__ void wt_seed_class(const WtVConst &vc, const WtClass 
     // R's rank block: its node's first o entries are the prefix part's elements in it (mk: their ranks' bits), so
     // the ranks >= R among them finish the counts, and those below R hold the part's predecessor when any are there
     MT belA[NS], belB[NS];
-    bool hitA[NS], hitB[NS], wrapA[NS], wrapB[NS];
+    bool hitA[NS], hitB[NS];
     uint32_t l0 = WT_NONE;
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
@@ -863,16 +1023,20 @@ __device__ __forceinline__ void wt_seed_class(const WtVConst &vc, const WtClass 
         const MT vA = MK::load(mk, sA[u] + (sA[u] >> BB) + qA[u]);
         const MT vB = MK::low(MK::inv(MK::load(mk, sB[u] + (sB[u] >> BB) + qB[u])), min(nv - sB[u], BW));
         const uint32_t bA = RA[u] & ~BM, bB = RB[u] & ~BM;
-        const uint32_t pA = hitA[u] ? bA + MK::top(belA[u]) : sA[u] + MK::top(vA);
-        const uint32_t pB = hitB[u] ? bB + MK::top(belB[u]) : sB[u] + MK::top(vB);
+        pA[u] = hitA[u] ? bA + MK::top(belA[u]) : sA[u] + MK::top(vA);
+        pB[u] = hitB[u] ? bB + MK::top(belB[u]) : sB[u] + MK::top(vB);
+    }
+    }
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
         if (d[u] > 0) {
-            const uint32_t t = Hm[u] + cm[pA] - (wrapA[u] ? m : 0u);
-            const uint64_t k = ((uint64_t)t << 32) | (0xffffffffu - ev[pA]);
+            const uint32_t t = Hm[u] + cm[pA[u]] - (wrapA[u] ? m : 0u);
+            const uint64_t k = ((uint64_t)t << 32) | (0xffffffffu - ev[pA[u]]);
             key[u] = k > key[u] ? k : key[u];
         }
         if (d[u] < n) {
-            const uint32_t t = Hm2[u] + cm[pB] - (wrapB[u] ? m : 0u);
-            const uint64_t k = ((uint64_t)t << 32) | (0xffffffffu - ev[pB]);
+            const uint32_t t = Hm2[u] + cm[pB[u]] - (wrapB[u] ? m : 0u);
+            const uint64_t k = ((uint64_t)t << 32) | (0xffffffffu - ev[pB[u]]);
             key[u] = k > key[u] ? k : key[u];
         }
         sum[u] += (uint64_t)d[u] * Hm[u] + (uint64_t)(n - d[u]) * Hm2[u];
@@ -934,7 +1098,7 @@ __device__ unsigned long long g_wt_trace[256][16][10];
 #else
 #define NMZ_WT_ATTR
 #endif
-template <bool BIG, int NS, int BB>
+template <bool BIG, int NS, int BB, bool PL = false>
 __global__ __launch_bounds__(1024) NMZ_WT_ATTR void k_replayable_sweep_wt(
     const uint32_t *__restrict__ bucket_off, const uint64_t *__restrict__ sorted_h0,
     const uint32_t *__restrict__ sorted_idx, const uint4 *__restrict__ table, uint32_t E,
@@ -1030,7 +1194,7 @@ __global__ __launch_bounds__(1024) NMZ_WT_ATTR void k_replayable_sweep_wt(
 #pragma unroll
         for (int u = 0; u < NS; ++u) sum[u] = key[u] = W[u] = 0;
         for (uint32_t c = 0; c < n_classes; ++c)
-            wt_seed_class<BIG, NS, BB>(vc, classes[c], img, row, h0, m, mu, m_k64, msh, sum, W, key);
+            wt_seed_class<BIG, NS, BB, PL>(vc, classes[c], img, row, h0, m, mu, m_k64, msh, sum, W, key);
         uint64_t km = 0;  // the chunk's largest sum, in the top-k's order (int64, as an order-preserving u64 key)
 #pragma unroll
         for (int u = 0; u < NS; ++u) {
@@ -1492,6 +1656,13 @@ static uint32_t wt_max_bb() {
     return (uint32_t)((v >= 5 && v <= 7) ? v : 6);
 }
 
+// rank-block planes (bb = 6) in place of a plan's levels: NMZ_WT_PLANES=0 keeps the levels (A/B and tests; read at
+// every plan build)
+static bool wt_planes_enabled() {
+    const char *e = ab_env("NMZ_WT_PLANES");
+    return !(e && std::string(e) == "0");
+}
+
 constexpr size_t WT_BUILD_LDS = WT_NMAX * 8 * 2 + WT_NMAX / 2 * 4 + 2 * (WT_NMAX / 32 + 4) * 4 + 520 * 4 +
                                 WT_BW * 8 + 16;
 
@@ -1517,7 +1688,7 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
         }
     }
     n_cls = (uint32_t)seg.size();
-    auto layout = [&](uint32_t bb) -> uint64_t {
+    auto layout = [&](uint32_t bb, bool planes) -> uint64_t {
     oc.assign(n_cls, WtClass{});
     uint64_t off = 0;
     for (uint32_t c = 0; c < n_cls; ++c) {
@@ -1529,7 +1700,7 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
         o.K = bitlen(o.n);  // 2^K > n >= every bound R
         o.nw = o.n / 32 + 1;
         o.o_lv = (uint32_t)off;
-        off += r16((uint64_t)wt_levels(o.K, bb) * o.nw * 8);
+        off += r16(planes ? 0 : (uint64_t)wt_levels(o.K, bb) * o.nw * 8);
         o.o_cm = (uint32_t)off;
         off += r16((uint64_t)(o.n + WT_PAD) * 4);
         o.o_chi = (uint32_t)off;
@@ -1542,13 +1713,24 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
         off += r16(256 * 2);
         o.o_mk = (uint32_t)off;
         off += r16(wt_mask_bytes(o.n, bb));
+        if (planes) {  // planes 0 .. (n >> 6) + 1 (never at offset 0: the segment's other arrays come first)
+            o.o_pl = (uint32_t)off;
+            off += r16(wt_plane_bytes(o.n, o.nw));
+        }
     }
     return off;
     };
     // the widest rank blocks whose row image fits LDS (NMZ_WT_BB caps the width, A/B and tests)
     uint32_t bb = wt_max_bb();
-    uint64_t off = layout(bb);
-    while (bb > 5 && std::max<uint64_t>(16, r16(off)) + 32 > WT_LDS_MAX) off = layout(--bb);
+    uint64_t off = layout(bb, false);
+    while (bb > 5 && std::max<uint64_t>(16, r16(off)) + 32 > WT_LDS_MAX) off = layout(--bb, false);
+    // 64-rank blocks: planes instead of levels while the image stays within WT_PLANES_MAX (NMZ_WT_PLANES=0: levels)
+    bool planes = false;
+    if (bb == 6 && wt_planes_enabled()) {
+        const uint64_t poff = layout(6, true);
+        planes = std::max<uint64_t>(16, r16(poff)) <= WT_PLANES_MAX;
+        off = planes ? poff : layout(6, false);
+    }
     {  // the plan kernel's dispatch order: segments by size, largest first
         std::vector<uint32_t> ord(n_cls);
         std::iota(ord.begin(), ord.end(), 0u);
@@ -1565,6 +1747,8 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
                               reinterpret_cast<const void *>(k_replayable_sweep_wt<true, 1, 6>),
                               reinterpret_cast<const void *>(k_replayable_sweep_wt<false, 1, 7>),
                               reinterpret_cast<const void *>(k_replayable_sweep_wt<true, 1, 7>),
+                              reinterpret_cast<const void *>(k_replayable_sweep_wt<false, 1, 6, true>),
+                              reinterpret_cast<const void *>(k_replayable_sweep_wt<true, 1, 6, true>),
                               reinterpret_cast<const void *>(k_replayable_wt_build<false, 5>),
                               reinterpret_cast<const void *>(k_replayable_wt_build<true, 5>),
                               reinterpret_cast<const void *>(k_replayable_wt_build<false, 6>),
@@ -1579,6 +1763,7 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
     }
     w.rb16 = (uint32_t)(rb / 16);
     w.bb = bb;
+    w.planes = planes;
     w.n_classes = n_cls;
     w.msh = mod.m32 > 255 ? bitlen(mod.m32) - 8 : 0;
     return true;
@@ -1659,9 +1844,13 @@ int wt_sweep(const WtState &w, nmz_ctx *ctx, hipStream_t st, const Buckets &b, c
     // one seed per lane: two (NS = 2, 106 VGPRs) measured slower, K1 span 0.074 vs 0.059 ms
     // (profiles/r04/k1_ns2_rejected/)
     auto kern = big ? (w.bb == 7 ? k_replayable_sweep_wt<true, WT_NS, 7>
-                       : w.bb == 6 ? k_replayable_sweep_wt<true, WT_NS, 6> : k_replayable_sweep_wt<true, WT_NS, 5>)
+                       : w.bb == 6 ? (w.planes ? k_replayable_sweep_wt<true, WT_NS, 6, true>
+                                               : k_replayable_sweep_wt<true, WT_NS, 6>)
+                                   : k_replayable_sweep_wt<true, WT_NS, 5>)
                     : (w.bb == 7 ? k_replayable_sweep_wt<false, WT_NS, 7>
-                       : w.bb == 6 ? k_replayable_sweep_wt<false, WT_NS, 6> : k_replayable_sweep_wt<false, WT_NS, 5>);
+                       : w.bb == 6 ? (w.planes ? k_replayable_sweep_wt<false, WT_NS, 6, true>
+                                               : k_replayable_sweep_wt<false, WT_NS, 6>)
+                                   : k_replayable_sweep_wt<false, WT_NS, 5>);
     const size_t lds = w.rb16 * 16u + 32u;
     hipLaunchKernelGGL(kern, dim3(256 * G), dim3(nt), lds, st, b.offset, b.sorted_h0, b.sorted_idx,
                        d_table, E, w.d_blob, w.rb16, w.d_rowsum, static_cast<const WtClass *>(w.d_classes),

@@ -305,3 +305,102 @@ def query_quantile(img, d, RA, RB, Hm, Hm2, m):
         t = (Hm2 + cm[pB] - (m if wrap else 0)) % (1 << 32)
         kB = (t << 32) | (0xFFFFFFFF - ev[pB])
     return W, kA, kB
+
+
+def build_planes(cm, e, chi):
+    """The plane form of the image (64-rank blocks): instead of levels, plane b (b = 0 .. NB, NB = (n >> 6) + 1) holds
+    bit i = [rank_i >= 64 b] in position order, stored like a level ({32 bits, ones before} per 32 positions), and the
+    blocks' prefix masks come straight from the ranks by position (no level pass orders them)."""
+    n = len(cm)
+    keys = sorted(((cm[i] << 32) | ((0xFFFF - e[i]) << 16) | i) for i in range(n))
+    cm_r = [k >> 32 for k in keys] + [0xFFFFFFFF]
+    e_r = [0xFFFF - ((k >> 16) & 0xFFFF) for k in keys]
+    S = [0] * n
+    for j, k in enumerate(keys):
+        S[k & 0xFFFF] = j
+    NB = (n >> 6) + 1
+    nw = n // 32 + 1
+    pl = []
+    for b in range(NB + 1):
+        wb = [0] * nw
+        for j in range(n):
+            if S[j] >> 6 >= b:
+                wb[j >> 5] |= 1 << (j & 31)
+        row, acc = [], 0
+        for w in range(nw):
+            row.append((wb[w], acc))
+            acc += bin(wb[w]).count("1")
+        pl.append(row)
+    mk = []
+    for b in range(NB):
+        row, acc = [0], 0
+        for j in range(n):  # the block's ranks in position order
+            if S[j] >> 6 == b:
+                acc |= 1 << (S[j] & 63)
+                row.append(acc)
+        row += [acc] * (65 - len(row))
+        mk.append(row)
+    return dict(n=n, NB=NB, nw=nw, pl=pl, mk=mk, cm=cm_r, e=e_r, chi=list(chi) + [0xFFFFFFFF], bb=6)
+
+
+def query_planes(img, d, RA, RB, Hm, Hm2, m):
+    """returns (W, keyA or None, keyB or None) following the plane form of wt_seed_class after the searches: counts
+    from two planes and a mask per chain, predecessors by a lifting search over blocks."""
+    n, NB, pl, mk, cm, ev = img["n"], img["NB"], img["pl"], img["mk"], img["cm"], img["e"]
+    F = (1 << 64) - 1
+
+    def f(b):  # f_b(d): one read of plane b
+        w = pl[b][d >> 5]
+        return w[1] + bin(w[0] & ((1 << (d & 31)) - 1)).count("1")
+
+    def top(x):
+        return x.bit_length() - 1
+
+    bA, rA, bB, rB = RA >> 6, RA & 63, RB >> 6, RB & 63
+    fA0, fA1, fB0, fB1 = f(bA), f(bA + 1), f(bB), f(bB + 1)
+    mA = mk[bA][fA0 - fA1]
+    mB = mk[bB][fB0 - fB1]
+    cA = fA1 + bin(mA >> rA).count("1")
+    cB = fB1 + bin(mB >> rB).count("1")
+    W = cA + (n - RB) - cB
+    belA = mA & ((1 << rA) - 1)
+    belB = (~mB & F) & ((1 << rB) - 1)
+    hitA, hitB = belA != 0, belB != 0
+    dA, dB = d > 0 and not hitA, d < n and not hitB
+    wrapA = dA and d == cA          # no prefix element below R_A
+    wrapB = dB and RB + cB == d     # no suffix element below R_B
+    OFF = 0x7FFFFFFF
+    posA, TA = (bA if wrapA else 0), (OFF if not dA else 0 if wrapA else fA0)
+    posB, TB = (bB if wrapB else 0), (OFF if not dB else 0 if wrapB else n - 64 * bB - fB0)
+    st = 32
+    while st:
+        if st < NB:
+            qa, qb = min(posA + st, NB), min(posB + st, NB)
+            if f(qa) > TA:
+                posA = qa
+            if n - 64 * qb - f(qb) > TB:  # signed: negative at qb = NB
+                posB = qb
+        st >>= 1
+    kA = kB = None
+    if d > 0:
+        if hitA:
+            pA = 64 * bA + top(belA)
+        else:
+            assert posA < NB and (wrapA or posA < bA)
+            v = mk[posA][f(posA) - f(posA + 1)]
+            assert v
+            pA = 64 * posA + top(v)
+        t = (Hm + cm[pA] - (m if wrapA else 0)) % (1 << 32)
+        kA = (t << 32) | (0xFFFFFFFF - ev[pA])
+    if d < n:
+        if hitB:
+            pB = 64 * bB + top(belB)
+        else:
+            assert posB < NB and (wrapB or posB < bB)
+            size = min(n - 64 * posB, 64)
+            v = (~mk[posB][f(posB) - f(posB + 1)] & F) & (F >> (64 - size))
+            assert v
+            pB = 64 * posB + top(v)
+        t = (Hm2 + cm[pB] - (m if wrapB else 0)) % (1 << 32)
+        kB = (t << 32) | (0xFFFFFFFF - ev[pB])
+    return W, kA, kB
