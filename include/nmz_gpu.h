@@ -849,6 +849,62 @@ int nmz_order_contrast(nmz_ctx *ctx, const uint32_t *pos, const uint8_t *failed,
                        uint32_t k, nmz_pair_counts *counts /* may be NULL */, nmz_order_pair *pairs,
                        nmz_contrast_info *info);
 
+/* ---- matching stored runs to the event universe: pos[n_runs][n_events] made on the device ------------------
+ * The reference walks its stored runs one by one (historystorage/naive/naive.go:235-257), each handed out by
+ * GetStoredHistory (historystorage/historystorage.go:45). These entry points turn the runs' symbol sequences into
+ * the pos array nmz_order_contrast* takes (and, one row, the target_pos of nmz_replayable_target_*), by the rule of
+ * match_target (namazu_amd/historystorage.py):
+ *     the universe is sym[n_events] (uint64) with arrival_ns[n_events] (int64);
+ *     the events carrying one symbol value are ordered by (arrival asc, event index asc), and occurrence j of that
+ *     order is "the j-th event with the symbol";
+ *     run r is the symbol slice run_sym[run_off[r] .. run_off[r + 1]);
+ *     the i-th occurrence of a value in the run (counting from 0 in run order), at run position p, is matched to the
+ *     i-th event with that value: pos[r][e] = p;
+ *     events without a matched occurrence get NMZ_NONE; run elements whose value is not in the universe, and
+ *     occurrences beyond the universe's count of that value, are ignored. Positions are indexes into the run, so a
+ *     row can have holes.
+ * Limits of the host forms, each NMZ_EINVAL with a message, checked before any device work: 1 <= n_events <=
+ * NMZ_DELIVERY_MAX_EVENTS; run_off[0] == 0 and the offsets non-decreasing; every run shorter than 2^32 - 1
+ * elements (NMZ_NONE stays free); n_runs * n_events fits the output. n_runs == 0 is legal and writes nothing. */
+
+/* One run on the calling host thread, no device work (naive.go:235-257, historystorage.go:45 GetStoredHistory):
+ * plain loops by the definition (a stable sort of the events by arrival, then for each run element the first
+ * unmatched event with its symbol); it shares no table or reduction with the kernel. pos[n_events]. */
+int nmz_match_run_host(const uint64_t *sym, const int64_t *arrival_ns, uint32_t n_events, const uint64_t *run_sym,
+                       uint64_t run_len, uint32_t *pos);
+/* The plan owns the universe's device tables (naive.go:235-257, historystorage.go:45 GetStoredHistory): the distinct
+ * symbols, each symbol's event list in (arrival, index) order, and the counts. Host arrays are borrowed for the
+ * call. A plan serves any number of matches on any streams; destroy waits for them. */
+typedef struct nmz_match_plan nmz_match_plan;
+int nmz_match_plan_create(nmz_ctx *ctx, const uint64_t *sym, const int64_t *arrival_ns, uint32_t n_events,
+                          nmz_match_plan **out);
+int nmz_match_plan_destroy(nmz_match_plan *plan);
+/* The plan's constants (naive.go:235-257, historystorage.go:45 GetStoredHistory): n_symbols = the number of distinct
+ * symbols; each pointer may be NULL. */
+int nmz_match_plan_info(const nmz_match_plan *plan, uint32_t *n_events, uint32_t *n_symbols);
+/* Device CSR in (naive.go:235-257, historystorage.go:45 GetStoredHistory): d_run_off[n_runs + 1] and d_run_sym, both
+ * uint64, the layout nmz_unique_traces_dev takes; row-major uint32 d_pos[n_runs][n_events] out, the array
+ * nmz_order_contrast_dev takes and, one row, a target_pos. Enqueued on `stream` (NULL = the context's). The host
+ * cannot read the offsets: they must be non-decreasing and stay inside d_run_sym (a decreasing pair reads as an
+ * empty run), and elements at run positions >= 2^32 - 1 are ignored. */
+int nmz_match_runs_dev(nmz_match_plan *plan, const uint64_t *d_run_off, const uint64_t *d_run_sym, uint64_t n_runs,
+                       uint32_t *d_pos, void *stream);
+/* Host pointers, synchronous, built on the _dev form (naive.go:235-257, historystorage.go:45 GetStoredHistory):
+ * plan + upload + match + pos[n_runs][n_events] back. The device buffers are taken for the call from the context's
+ * pool. */
+int nmz_match_runs(nmz_ctx *ctx, const uint64_t *sym, const int64_t *arrival_ns, uint32_t n_events,
+                   const uint64_t *run_off, const uint64_t *run_sym, uint64_t n_runs, uint32_t *pos);
+/* nmz_order_contrast from the stored runs themselves (naive.go:235-257, historystorage.go:45 GetStoredHistory; the
+ * labels naive.go:199-213): host pointers, synchronous. The CSR is uploaded, matched on the device and fed to
+ * nmz_order_contrast_dev; pos never leaves the device. Its [n_runs][n_events] rows (up to 1 GB) are taken for the
+ * call from the context's pool, not from the contrast's fixed scratch. Every limit and label check of
+ * nmz_order_contrast and of nmz_match_runs holds, with the same messages, before any device work. counts, pairs and
+ * info may each be NULL. The results are byte-identical to nmz_order_contrast over nmz_match_runs' output. */
+int nmz_order_contrast_runs(nmz_ctx *ctx, const uint64_t *sym, const int64_t *arrival_ns, uint32_t n_events,
+                            const uint64_t *run_off, const uint64_t *run_sym, const uint8_t *failed, uint32_t n_runs,
+                            uint32_t k, nmz_pair_counts *counts /* may be NULL */, nmz_order_pair *pairs,
+                            nmz_contrast_info *info);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

@@ -178,6 +178,13 @@ SIGNATURES = {
     "nmz_order_contrast": (_int, [_P, _P, _P, _u32, _u32, _u32, _P, _P, _P]),
     "nmz_replayable_target_sweep_decimal": (_int, [_P, _u64, _u64, _P, _P, _u32, _i64, _P, _P, _P, _int, _u32, _P,
                                                    _P, _P, _P]),
+    "nmz_match_run_host": (_int, [_P, _P, _u32, _P, _u64, _P]),
+    "nmz_match_plan_create": (_int, [_P, _P, _P, _u32, ctypes.POINTER(_P)]),
+    "nmz_match_plan_destroy": (_int, [_P]),
+    "nmz_match_plan_info": (_int, [_P, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "nmz_match_runs_dev": (_int, [_P, _P, _P, _u64, _P, _P]),
+    "nmz_match_runs": (_int, [_P, _P, _P, _u32, _P, _P, _u64, _P]),
+    "nmz_order_contrast_runs": (_int, [_P, _P, _P, _u32, _P, _P, _P, _u32, _u32, _P, _P, _P]),
     "nmz_trace_signatures": (_int, [_P, _P, _P, _P, _u32, _P]),
     "nmz_unique_traces": (_int, [_P, _P, _P, _P, _u32, _P]),
     "nmz_unique_traces_dev": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _P, _P]),

@@ -387,4 +387,45 @@ int nmz_order_contrast(nmz_ctx *ctx, const uint32_t *pos, const uint8_t *failed,
     return NMZ_OK;
 }
 
+// From the stored runs themselves (naive.go:235-257, historystorage.go:45 GetStoredHistory; labels naive.go:199-213):
+// the CSR goes up, K7 (match.hip) makes pos on the device and the contrast reads it there. The rows are taken for
+// the call from the context's pool, not from the contrast's scratch.
+int nmz_order_contrast_runs(nmz_ctx *ctx, const uint64_t *sym, const int64_t *arrival_ns, uint32_t n_events,
+                            const uint64_t *run_off, const uint64_t *run_sym, const uint8_t *failed, uint32_t n_runs,
+                            uint32_t k, nmz_pair_counts *counts, nmz_order_pair *pairs, nmz_contrast_info *info) {
+    // the arguments first: they are checked without a device
+    NMZ_TRY(contrast_limits(n_runs, n_events));
+    NMZ_CHECK(k <= 256, "top-k supports k <= 256");
+    NMZ_TRY(match_validate(sym, arrival_ns, n_events, run_off, run_sym, n_runs));
+    NMZ_CHECK(failed != nullptr, "failed is NULL");
+    uint32_t n_fail = 0;
+    NMZ_TRY(contrast_labels(failed, n_runs, &n_fail));
+    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
+    if (!pairs) k = 0;
+    CtxGuard g(ctx);
+    NMZ_TRY(g.rc);
+    hipStream_t st = ctx->stream;
+    nmz_contrast_info hinfo{};
+    MatchCall call(ctx);  // behind hinfo: its destructor drains the stream that copies into it
+    const size_t sq = (size_t)n_events * n_events;
+    NMZ_TRY(ctx->buf[19].ensure(Carve::bytes_for(n_runs, 1) + Carve::bytes_for(counts ? sq : 1, sizeof(nmz_pair_counts)) +
+                                Carve::bytes_for(k + 1, sizeof(nmz_order_pair)) +
+                                Carve::bytes_for(1, sizeof(nmz_contrast_info))));
+    Carve cv(ctx->buf[19].ptr);
+    uint8_t *d_failed = cv.take<uint8_t>(n_runs);
+    nmz_pair_counts *d_counts = cv.take<nmz_pair_counts>(counts ? sq : 1);
+    nmz_order_pair *d_pairs = cv.take<nmz_order_pair>(k + 1);
+    nmz_contrast_info *d_info = cv.take<nmz_contrast_info>(1);
+    uint32_t *d_pos = nullptr;
+    NMZ_TRY(call.run(sym, arrival_ns, n_events, run_off, run_sym, n_runs, &d_pos));
+    NMZ_HIP(hipMemcpyAsync(d_failed, failed, n_runs, hipMemcpyHostToDevice, st));
+    NMZ_TRY(contrast_run(ctx, st, d_pos, d_failed, n_runs, n_events, k, counts ? d_counts : nullptr, d_pairs, d_info));
+    if (counts) NMZ_HIP(hipMemcpyAsync(counts, d_counts, sq * sizeof(nmz_pair_counts), hipMemcpyDeviceToHost, st));
+    if (k) NMZ_HIP(hipMemcpyAsync(pairs, d_pairs, k * sizeof(nmz_order_pair), hipMemcpyDeviceToHost, st));
+    NMZ_HIP(hipMemcpyAsync(&hinfo, d_info, sizeof(hinfo), hipMemcpyDeviceToHost, st));
+    NMZ_HIP(hipStreamSynchronize(st));
+    if (info) *info = hinfo;
+    return NMZ_OK;
+}
+
 }  // extern "C"

@@ -33,4 +33,20 @@ int device_unique_u64(const uint64_t *d_sym, uint64_t total, uint64_t *d_uniq, u
 int sig_rank_keys(nmz_ctx *ctx, const ulonglong2 **out);
 int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_first, hipStream_t st);
 
+// match.hip, for contrast.hip (nmz_order_contrast_runs). match_validate: every limit of the host forms, no device.
+int match_validate(const uint64_t *sym, const int64_t *arrival, uint32_t E, const uint64_t *run_off,
+                   const uint64_t *run_sym, uint64_t n_runs);
+// One host-form match on the context's stream; the caller holds ctx and has validated. run() builds the universe's
+// plan, takes rows, offsets and symbols from the context's pool for the call, uploads the CSR and enqueues the
+// match: *d_pos = the [n_runs][E] rows. The destructor drains the stream before plan and buffer go back.
+struct MatchCall {
+    nmz_ctx *ctx;
+    nmz_match_plan *plan = nullptr;
+    DevBuf work;
+    explicit MatchCall(nmz_ctx *c) : ctx(c) { work.pool = &c->pool; }
+    ~MatchCall();
+    int run(const uint64_t *sym, const int64_t *arrival, uint32_t E, const uint64_t *run_off,
+            const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos);
+};
+
 }  // namespace nmz

@@ -260,8 +260,9 @@ class Naive(HistoryStorage):
             ids.append(i)
             runs.append(t)
             failed.append(0 if ok else 1)
-        pos = run_positions(sym, arrival_ns, runs)
-        c = order_contrast(pos, np.array(failed, np.uint8), k=k, want_counts=want_counts, ctx=ctx)
+        # the matching runs on the device too: equal by definition to order_contrast(run_positions(...), ...)
+        c = order_contrast_runs(sym, arrival_ns, runs, np.array(failed, np.uint8), k=k, want_counts=want_counts,
+                                ctx=ctx)
         c.run_ids = ids
         return c
 
@@ -484,19 +485,23 @@ class ContrastResult:
         self.run_ids = None  # Naive.OrderContrast: the stored runs behind the rows
 
 
-def _contrast_inputs(pos, failed):
-    pos = np.ascontiguousarray(pos, np.uint32)
-    if pos.ndim != 2:
-        raise ValueError(f"pos must be [runs][events], got shape {pos.shape}")
+def _contrast_labels(failed, n_runs):
     failed = np.asarray(failed)
     if failed.dtype == np.bool_:
         failed = failed.astype(np.uint8)
     elif failed.size and (failed.min() < 0 or failed.max() > 255):
         raise ValueError("failed holds a label outside uint8")
     failed = np.ascontiguousarray(failed, np.uint8).reshape(-1)
-    if len(failed) != pos.shape[0]:
-        raise ValueError(f"{len(failed)} labels for {pos.shape[0]} runs")
-    return pos, failed
+    if len(failed) != n_runs:
+        raise ValueError(f"{len(failed)} labels for {n_runs} runs")
+    return failed
+
+
+def _contrast_inputs(pos, failed):
+    pos = np.ascontiguousarray(pos, np.uint32)
+    if pos.ndim != 2:
+        raise ValueError(f"pos must be [runs][events], got shape {pos.shape}")
+    return pos, _contrast_labels(failed, pos.shape[0])
 
 
 def run_positions(sym, arrival_ns, traces):
@@ -535,6 +540,99 @@ def order_contrast(pos, failed, k=64, want_counts=False, ctx=None):
     info = np.zeros(1, _lib.CONTRAST_INFO_DTYPE)
     _lib.check(_lib.load().nmz_order_contrast(ctx.handle, _lib.ptr(pos), _lib.ptr(failed), R, E, k, _lib.ptr(counts),
                                               _lib.ptr(pairs) if k else None, _lib.ptr(info)))
+    return ContrastResult(pairs, counts, int(info[0]["n_fail"]), int(info[0]["n_pass"]), int(info[0]["n_positive"]))
+
+
+def _universe(sym, arrival_ns):
+    sym = np.ascontiguousarray(sym, np.uint64).reshape(-1)
+    arr = np.ascontiguousarray(arrival_ns, np.int64).reshape(-1)
+    if len(arr) != len(sym):
+        raise ValueError(f"{len(arr)} arrival times for {len(sym)} symbols")
+    return sym, arr
+
+
+def _run_set(traces):
+    if isinstance(traces, TraceSet):
+        return traces
+    return TraceSet([t.symbols if isinstance(t, SingleTrace) else np.asarray(t, np.uint64).reshape(-1)
+                     for t in traces])
+
+
+def match_run_host(sym, arrival_ns, recorded_sym):
+    """match_target's row on the host through nmz_match_run_host (no GPU): plain loops by the definition, sharing
+    nothing with the kernel or with match_target's numpy."""
+    sym, arr = _universe(sym, arrival_ns)
+    rec = np.ascontiguousarray(recorded_sym, np.uint64).reshape(-1)
+    out = np.zeros(len(sym), np.uint32)
+    _lib.check(_lib.load().nmz_match_run_host(_lib.ptr(sym), _lib.ptr(arr), len(sym), _lib.ptr(rec), len(rec),
+                                              _lib.ptr(out)))
+    return out
+
+
+class MatchPlan:
+    """The event universe (sym, arrival_ns) resident on the GPU (nmz_match_plan): runs_dev matches a device CSR of
+    recorded runs into a device pos[n_runs][E], the array nmz_order_contrast_dev and target_pos take."""
+
+    def __init__(self, sym, arrival_ns, ctx=None):
+        self.ctx = ctx or _lib.default_context()
+        sym, arr = _universe(sym, arrival_ns)
+        self.plan = ctypes.c_void_p()
+        L = _lib.load()
+        _lib.check(L.nmz_match_plan_create(self.ctx.handle, _lib.ptr(sym), _lib.ptr(arr), len(sym),
+                                           ctypes.byref(self.plan)))
+        e, u = ctypes.c_uint32(), ctypes.c_uint32()
+        _lib.check(L.nmz_match_plan_info(self.plan, ctypes.byref(e), ctypes.byref(u)))
+        self.n_events, self.n_symbols = e.value, u.value
+
+    def runs_dev(self, d_run_off, d_run_sym, n_runs, d_pos, stream=None):
+        """Device pointers (ints): uint64 offsets[n_runs + 1] and symbols in, uint32 pos[n_runs][E] out, enqueued
+        on `stream` (a HIP stream handle; None = the context's)."""
+        _lib.check(_lib.load().nmz_match_runs_dev(self.plan, ctypes.c_void_p(d_run_off), ctypes.c_void_p(d_run_sym),
+                                                  int(n_runs), ctypes.c_void_p(d_pos),
+                                                  ctypes.c_void_p(stream) if stream else None))
+
+    def close(self):
+        if self.plan:
+            _lib.load().nmz_match_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match_runs(sym, arrival_ns, traces, ctx=None):
+    """run_positions on the GPU (nmz_match_runs): pos[len(traces)][len(sym)] (uint32), one match_target row per
+    recorded run (SingleTraces, event-symbol arrays or a TraceSet) against the event universe (sym, arrival_ns)."""
+    sym, arr = _universe(sym, arrival_ns)
+    ts = _run_set(traces)
+    out = np.full((len(ts), len(sym)), _lib.NMZ_NONE, np.uint32)
+    ctx = ctx or _lib.default_context()
+    _lib.check(_lib.load().nmz_match_runs(ctx.handle, _lib.ptr(sym), _lib.ptr(arr), len(sym), _lib.ptr(ts.off),
+                                          _lib.ptr(ts.sym), len(ts), _lib.ptr(out)))
+    return out
+
+
+def order_contrast_runs(sym, arrival_ns, traces, failed, k=64, want_counts=False, ctx=None):
+    """order_contrast(run_positions(sym, arrival_ns, traces), failed, ...) with the matching on the GPU too
+    (nmz_order_contrast_runs): the runs' symbols go up, pos is made and read on the device and never comes back.
+    Returns the same ContrastResult, byte for byte."""
+    sym, arr = _universe(sym, arrival_ns)
+    ts = _run_set(traces)
+    failed = _contrast_labels(failed, len(ts))
+    E = len(sym)
+    k = int(k)
+    if not 0 <= k < 2**32:
+        raise ValueError(f"k = {k} does not fit uint32")
+    ctx = ctx or _lib.default_context()
+    pairs = np.zeros(k, _lib.ORDER_PAIR_DTYPE)
+    counts = np.zeros((E, E), _lib.PAIR_COUNTS_DTYPE) if want_counts else None
+    info = np.zeros(1, _lib.CONTRAST_INFO_DTYPE)
+    _lib.check(_lib.load().nmz_order_contrast_runs(ctx.handle, _lib.ptr(sym), _lib.ptr(arr), E, _lib.ptr(ts.off),
+                                                   _lib.ptr(ts.sym), _lib.ptr(failed), len(ts), k, _lib.ptr(counts),
+                                                   _lib.ptr(pairs) if k else None, _lib.ptr(info)))
     return ContrastResult(pairs, counts, int(info[0]["n_fail"]), int(info[0]["n_pass"]), int(info[0]["n_positive"]))
 
 

@@ -257,6 +257,53 @@ static void delivery_cases() {
                                                 nullptr, &st, u, u, u) == NMZ_EINVAL);
 }
 
+// the run match's host form and the limits of its host-pointer forms (all refused before a context is needed)
+static void match_cases() {
+    const uint64_t sym[5] = {5, 7, 5, 9, 5};
+    const int64_t arrival[5] = {10, 0, 3, 1, 3};
+    const uint64_t run[6] = {5, 5, 7, 8, 5, 5};
+    uint32_t pos[5];
+    CHECK(nmz_match_run_host(sym, arrival, 5, run, 6, pos) == NMZ_OK);
+    CHECK(pos[0] == 4 && pos[1] == 2 && pos[2] == 0 && pos[3] == NMZ_NONE && pos[4] == 1);
+    CHECK(nmz_match_run_host(sym, arrival, 5, nullptr, 0, pos) == NMZ_OK && pos[0] == NMZ_NONE && pos[4] == NMZ_NONE);
+    // a full-size universe of one symbol, over-filled: every position once
+    std::vector<uint64_t> one(4096, 42), many(5000, 42);
+    std::vector<int64_t> arr(4096);
+    std::vector<uint32_t> p(4096);
+    for (int i = 0; i < 4096; ++i) arr[i] = (i * 7) % 64;
+    CHECK(nmz_match_run_host(one.data(), arr.data(), 4096, many.data(), many.size(), p.data()) == NMZ_OK);
+    std::vector<char> seen(4096, 0);
+    for (uint32_t v : p) {
+        CHECK(v < 4096 && !seen[v]);
+        if (v < 4096) seen[v] = 1;
+    }
+    CHECK(nmz_match_run_host(sym, arrival, 0, run, 6, pos) == NMZ_EINVAL);
+    CHECK(nmz_match_run_host(sym, arrival, 5, run, 0xFFFFFFFFull, pos) == NMZ_EINVAL);
+    CHECK(nmz_match_run_host(sym, arrival, 5, run, 6, nullptr) == NMZ_EINVAL);
+    const uint64_t off[3] = {0, 2, 6}, bad0[3] = {1, 2, 6}, dec[3] = {0, 4, 2};
+    uint32_t rows[10];
+    const uint8_t failed[2] = {1, 0};
+    nmz_order_pair pairs[4];
+    CHECK(nmz_match_runs(nullptr, sym, arrival, 5, off, run, 2, rows) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL"));
+    CHECK(nmz_match_runs(nullptr, sym, arrival, 5, bad0, run, 2, rows) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "run_off[0]"));
+    CHECK(nmz_match_runs(nullptr, sym, arrival, 5, dec, run, 2, rows) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "non-decreasing"));
+    CHECK(nmz_match_runs(nullptr, sym, arrival, 5, off, run, 1ull << 63, rows) == NMZ_EINVAL);
+    CHECK(nmz_match_runs(nullptr, sym, arrival, 5, nullptr, nullptr, 0, nullptr) == NMZ_OK);
+    CHECK(nmz_order_contrast_runs(nullptr, sym, arrival, 5, off, run, failed, 2, 4, nullptr, pairs, nullptr) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL"));
+    CHECK(nmz_order_contrast_runs(nullptr, sym, arrival, 5, dec, run, failed, 2, 4, nullptr, pairs, nullptr) ==
+          NMZ_EINVAL);
+    nmz_match_plan *plan = nullptr;
+    CHECK(nmz_match_plan_create(nullptr, sym, arrival, 5, &plan) == NMZ_EINVAL && plan == nullptr);
+    CHECK(nmz_match_plan_destroy(nullptr) == NMZ_OK);
+    CHECK(nmz_match_plan_info(nullptr, nullptr, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_match_runs_dev(nullptr, off, run, 2, rows, nullptr) == NMZ_EINVAL);
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -306,6 +353,7 @@ int main() {
     procset_cases();
     order_cases();
     delivery_cases();
+    match_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
