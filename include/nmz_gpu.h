@@ -599,7 +599,8 @@ int nmz_debug_tp_offsets(nmz_ctx *ctx, const uint32_t *d_cnt, uint32_t n, uint32
  *       subsequence is equal.
  * sig[2*n_traces]: 128-bit signature per trace (equal traces -> equal signatures; distinct
  * ones collide with probability ~2^-128). first_equal[i] = the smallest j with sig_j == sig_i
- * (j <= i), so the unique-trace curve of visualize is the running count of first_equal[i] == i. */
+ * (j <= i), so the unique-trace curve of visualize is the running count of first_equal[i] == i.
+ * Both refuse decreasing offsets (NMZ_EINVAL, "offsets must be non-decreasing"), before the context is looked at. */
 int nmz_trace_signatures(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
                          uint32_t n_traces, uint64_t *sig);
 int nmz_unique_traces(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,

@@ -102,9 +102,9 @@ __global__ __launch_bounds__(256) void k_trace_sig(const uint64_t *__restrict__ 
     bool pend = false;  // SIG_PIPE: the previous step's element, its keys gathered, not yet mixed
     uint64_t ps = 0;
     ulonglong2 pk = make_ulonglong2(0ull, 0ull);
-    // PO mode: SIG_U steps' loads in flight per wave (one step at a time, the rank step's LDS round trip and the
-    // next load's latency did not overlap: 0.73 -> 0.65 ms for 100k x 2,048); exact mode one step (measured
-    // 3 % slower with four)
+    // both modes: four steps' loads in flight per wave (SIG_U for PO, NMZ_SIG_UX for exact), and the SIG_PIPE batching
+    // below applies to both (PO, one step at a time: the rank step's LDS round trip and the next load's latency did
+    // not overlap, 0.73 -> 0.65 ms for 100k x 2,048)
     constexpr uint32_t U = PO ? SIG_U : NMZ_SIG_UX;
     for (uint64_t c0 = 0; c0 < n; c0 += 64 * U) {
       uint64_t sv[U];
@@ -478,6 +478,16 @@ int device_unique_u64(const uint64_t *d_sym, uint64_t total, uint64_t *d_uniq, u
     return rc == NMZ_OK ? NMZ_OK : fail(NMZ_EHIP, "device distinct-symbol set failed");
 }
 
+// the argument checks of the two host entry points, ahead of the context check: a refusal needs no device
+static int traces_check_args(const uint64_t *off, const uint64_t *sym, const void *out, uint32_t n_traces) {
+    if (n_traces == 0) return NMZ_OK;
+    NMZ_CHECK(off && out, "NULL argument");
+    // a decreasing pair would wrap the kernel's n = off[t + 1] - off[t]
+    for (uint32_t i = 0; i < n_traces; ++i) NMZ_CHECK(off[i] <= off[i + 1], "offsets must be non-decreasing");
+    NMZ_CHECK(off[n_traces] == 0 || sym, "sym is NULL");
+    return NMZ_OK;
+}
+
 }  // namespace nmz
 
 using namespace nmz;
@@ -486,13 +496,12 @@ extern "C" {
 
 int nmz_trace_signatures(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
                          uint32_t n_traces, uint64_t *sig) {
+    NMZ_TRY(traces_check_args(off, sym, sig, n_traces));
     NMZ_CHECK(ctx != nullptr, "ctx is NULL");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     if (n_traces == 0) return NMZ_OK;
-    NMZ_CHECK(off && sig, "NULL argument");
     const uint64_t total = off[n_traces];
-    NMZ_CHECK(total == 0 || sym, "sym is NULL");
     uint32_t max_ent = 0;
     if (entity)
         for (uint64_t i = 0; i < total; ++i)
@@ -516,14 +525,12 @@ int nmz_trace_signatures(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym,
 
 int nmz_unique_traces(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
                       uint32_t n_traces, uint32_t *first_equal) {
+    NMZ_TRY(traces_check_args(off, sym, first_equal, n_traces));
     NMZ_CHECK(ctx != nullptr, "ctx is NULL");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     if (n_traces == 0) return NMZ_OK;
-    NMZ_CHECK(off && first_equal, "NULL argument");
     const uint64_t total = off[n_traces];
-    NMZ_CHECK(total == 0 || sym, "sym is NULL");
-    for (uint32_t i = 0; i < n_traces; ++i) NMZ_CHECK(off[i] <= off[i + 1], "offsets must be non-decreasing");
     uint32_t max_ent = 0;
     if (entity)
         for (uint64_t i = 0; i < total; ++i)

@@ -69,6 +69,14 @@ static void null_ctx_cases() {
     CHECK(nmz_trace_signatures(nullptr, o64, s64, nullptr, 1, sig) == NMZ_EINVAL);
     CHECK(nmz_unique_traces(nullptr, o64, s64, nullptr, 1, u32) == NMZ_EINVAL);
     CHECK(nmz_unique_traces_dev(nullptr, o64, s64, nullptr, 1, 0, sig, u32, nullptr) == NMZ_EINVAL);
+    // decreasing offsets are refused before the context is looked at (the last pair, the first pair)
+    uint64_t dec[4] = {0, 1, 1, 0}, dec0[3] = {1, 0, 1}, sig6[6];
+    CHECK(nmz_trace_signatures(nullptr, dec, s64, nullptr, 3, sig6) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "offsets must be non-decreasing") != nullptr);
+    CHECK(nmz_unique_traces(nullptr, dec0, s64, nullptr, 2, u32) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "offsets must be non-decreasing") != nullptr);
+    CHECK(nmz_trace_signatures(nullptr, o64, s64, nullptr, 1, sig) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
     CHECK(nmz_timing_enable(nullptr, 1) == NMZ_EINVAL);
     double ms;
     uint64_t cnt;
