@@ -1,6 +1,6 @@
 // K1 (replayable sweep) declarations shared by its translation units: the plan and the prepared seed set, and the
 // entry points of each kernel family -- seed prefixes (replayable_seeds.hip), per-decision sweeps
-// (replayable_pd.hip), order-query statistics (replayable_oq.hip), wavelet-tree statistics (replayable_wt.hip).
+// (replayable_pd.hip), order-query statistics (replayable_oq.hip), wavelet-tree statistics (replayable_wt_plan.hip, replayable_wt.hip).
 // replayable.hip holds the plan's build, the dispatch and the C ABI.
 #pragma once
 #include <array>
@@ -84,12 +84,12 @@ int oq_build(OqState &o, const uint4 *d_table, uint32_t E, const ModParams &mod,
 int oq_sweep(const OqState &o, nmz_ctx *ctx, hipStream_t st, const Buckets &b, const uint4 *d_table, uint32_t E,
              const ModParams &mod, nmz_sched_stats *d_stats);
 
-// ---- K1 wavelet-tree statistics (replayable_wt.hip): per-row images built once per plan, staged into LDS per
-// sweep ----
+// ---- K1 wavelet-tree statistics: per-row images built once per plan (replayable_wt_plan.hip), staged into LDS per
+// sweep (replayable_wt.hip, with the top-k selection of replayable_wt_topk_dev.h) ----
 struct WtState {
     bool on = false;
     uint32_t rb16 = 0, n_classes = 0, msh = 0;
-    uint32_t bb = 5;                        // rank blocks of 2^bb ranks below the tree's levels (replayable_wt.hip)
+    uint32_t bb = 5;                        // rank blocks of 2^bb ranks below the tree's levels (replayable_wt_dev.h)
     bool planes = false;                    // rank-block planes instead of levels (bb = 6, every segment or none)
     uint4 *d_blob = nullptr;                // [256][rb16] row images
     unsigned long long *d_rowsum = nullptr;  // [256] sum of C mod m over the row

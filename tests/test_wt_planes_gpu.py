@@ -17,7 +17,7 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-PLANES_MAX = 128 * 1024  # csrc/replayable_wt.hip: WT_PLANES_MAX
+PLANES_MAX = 128 * 1024  # csrc/replayable_wt_dev.h: WT_PLANES_MAX
 MS = (3, 1000, 100_000_000, 2**31 + 5)
 SEEDS = [str(i * 7919 + 1) for i in range(4096)]
 

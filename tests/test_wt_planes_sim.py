@@ -1,6 +1,6 @@
 """K1's rank-block planes restated on the host (tools/wt_sim.py build_planes / query_planes) against per-event
 decisions: counts from two planes and a mask, predecessors by the lifting search over blocks. A design check of the
-plane form of replayable_wt.hip, CPU only. Sizes: no block boundary inside the segment (one block), a last block of
+plane form of replayable_wt_plan.hip (build) and replayable_wt.hip (queries), CPU only. Sizes: no block boundary inside the segment (one block), a last block of
 one rank or none, more than one 32-position word, 64 blocks (the deepest search); moduli that force ties and wholly
 wrapping parts (3) and sums past 2^32."""
 import os

@@ -1,5 +1,6 @@
 """K1's wavelet-tree layout and descents restated on the host (tools/wt_sim.py) against per-event decisions, for
-every rank-block width the plan can take (32, 64 and 128 ranks). A design check of replayable_wt.hip, CPU only."""
+every rank-block width the plan can take (32, 64 and 128 ranks). A design check of replayable_wt_plan.hip (the layout) and
+replayable_wt.hip (the descents), CPU only."""
 import os
 import random
 import sys

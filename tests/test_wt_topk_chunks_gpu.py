@@ -18,7 +18,7 @@ from oracle import oracle as O
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WT_CAND = 4096  # csrc/replayable_wt.hip: the candidate arrays (and the list of flagged chunks)
+WT_CAND = 4096  # csrc/replayable_wt_dev.h: the candidate arrays (and the list of flagged chunks)
 
 
 def zk_hints(n, seed):

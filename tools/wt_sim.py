@@ -1,4 +1,4 @@
-"""Host simulation of K1's wavelet-tree statistics (namazu_amd/csrc/replayable_wt.hip), step for step, against
+"""Host simulation of K1's wavelet-tree statistics (the plan of namazu_amd/csrc/replayable_wt_plan.hip and the sweep of replayable_wt.hip), step for step, against
 per-event decisions. A design check for the plan layout and the descents -- not the product, not the oracle.
 
 usage: python tools/wt_sim.py [trials]
