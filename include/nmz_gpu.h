@@ -34,6 +34,9 @@
  *                             SearchWithConverter, historystorage/historystorage.go:50-51,
  *                             naive/naive.go:235-257); distance 0 <=> SingleTrace.Equals
  *                             (util/trace/trace.go:29-31).
+ *   nmz_ed_align_*         -> the same interface, extended: the edit script between
+ *                             two traces (which events moved, are missing or were
+ *                             replaced); an empty script <=> SingleTrace.Equals.
  *
  * Buffers passed to the host-pointer entry points are borrowed for the call
  * only and never retained (cgo pointer rules). The *_dev entry points take
@@ -905,6 +908,62 @@ int nmz_order_contrast_runs(nmz_ctx *ctx, const uint64_t *sym, const int64_t *ar
                             const uint64_t *run_off, const uint64_t *run_sym, const uint8_t *failed, uint32_t n_runs,
                             uint32_t k, nmz_pair_counts *counts /* may be NULL */, nmz_order_pair *pairs,
                             nmz_contrast_info *info);
+
+/* ---- edit scripts for trace pairs: what differs between two stored runs ------------------------------------
+ * A build-defined extension of the optional similarity interface (historystorage/historystorage.go:50-51); the
+ * reference has equality only (naive/naive.go:235-257), and an empty script <=> SingleTrace.Equals
+ * (util/trace/trace.go:29-31). For traces a (n symbols) and b (m symbols) and a band w:
+ *     dist = ED_w(a, b) = min(Lev(a, b), w + 1), exactly nmz_ed_pairs' value; dist == w + 1: no script;
+ *     otherwise the script is the canonical optimal alignment over the unit-cost Levenshtein matrix D: walk back
+ *     from (n, m) to (0, 0) taking at (i, j) the first move that applies --
+ *       1. diagonal: i, j > 0 and D[i-1][j-1] + (a[i-1] != b[j-1]) == D[i][j]: a match (no op) or NMZ_EDIT_SUB;
+ *       2. up: i > 0 and D[i-1][j] + 1 == D[i][j]: NMZ_EDIT_DEL;
+ *       3. left otherwise: NMZ_EDIT_INS;
+ *     the ops in forward order, matches omitted: exactly dist ops. a_pos / b_pos are the numbers of elements of a
+ *     and b consumed before the op. The script turns a into b; script(b, a) need not mirror it.
+ * Output per pair: `band` slots, the ops, then {NMZ_NONE, NMZ_NONE, NMZ_NONE}. Pair (ia, ib) aligns a = trace ia to
+ * b = trace ib. Limits, each NMZ_EINVAL with a message, checked before any device work (arguments before the
+ * context): band <= NMZ_ALIGN_MAX_BAND (wider bands are not built yet); traces shorter than 2^32 - 1 elements; pair
+ * indexes < n_traces; offsets non-decreasing. n_pairs == 0 is legal and needs no device; band == 0 is legal (dist in
+ * {0, 1}, ops may be NULL). */
+#define NMZ_ALIGN_MAX_BAND 64
+#define NMZ_EDIT_SUB 0u /* a[a_pos] becomes b[b_pos]                                  */
+#define NMZ_EDIT_DEL 1u /* a[a_pos] is dropped                                        */
+#define NMZ_EDIT_INS 2u /* b[b_pos] is inserted before a[a_pos]; a_pos may be n       */
+typedef struct nmz_edit_op {
+    uint32_t a_pos;
+    uint32_t b_pos;
+    uint32_t kind;
+} nmz_edit_op;
+/* One pair on the calling host thread, no device work (historystorage.go:50-51, naive.go:235-257,
+ * util/trace/trace.go:29-31): a plain +inf-banded DP that keeps its band rows, then the walk above. It shares no
+ * table or reduction with the kernel: the form to vet a script with, and the check of the device forms. */
+int nmz_ed_align_host(const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m, uint32_t band,
+                      uint32_t *dist, nmz_edit_op *ops /* [band] */);
+/* The plan owns the history scratch (historystorage.go:50-51, naive.go:235-257, util/trace/trace.go:29-31): 2 bits
+ * per band cell and row, for `slots` pairs in flight of up to max_len elements each, 256 MiB at the most in all. A
+ * max_len whose single pair exceeds that is NMZ_EINVAL. The plan serves one stream at a time (a launch on another
+ * stream waits for the one before); destroy waits for its launches. */
+typedef struct nmz_ed_align_plan nmz_ed_align_plan;
+int nmz_ed_align_plan_create(nmz_ctx *ctx, uint32_t band, uint64_t max_len, nmz_ed_align_plan **out);
+int nmz_ed_align_plan_destroy(nmz_ed_align_plan *plan);
+/* The plan's constants (historystorage.go:50-51, naive.go:235-257, util/trace/trace.go:29-31): the pairs in flight
+ * and the bytes of history scratch behind them; each pointer may be NULL. */
+int nmz_ed_align_plan_info(const nmz_ed_align_plan *plan, uint32_t *slots, uint64_t *history_bytes);
+/* Device CSR and device pairs in, d_dist[n_pairs] and d_ops[n_pairs * band] out (historystorage.go:50-51,
+ * naive.go:235-257, util/trace/trace.go:29-31); enqueued on `stream` (NULL = the context's), nothing else. The host
+ * cannot read the offsets: they must be non-decreasing and stay inside d_sym, the pair indexes below the number of
+ * traces (a decreasing pair of offsets reads as an empty trace), and a pair with a trace longer than the plan's
+ * max_len gets dist = NMZ_NONE and sentinel ops. */
+int nmz_ed_align_pairs_dev(nmz_ed_align_plan *plan, const uint64_t *d_off, const uint64_t *d_sym,
+                           const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist,
+                           nmz_edit_op *d_ops /* [n_pairs * band] */, void *stream);
+/* Host pointers, synchronous, built on the _dev form (historystorage.go:50-51, naive.go:235-257,
+ * util/trace/trace.go:29-31): a plan for the longest trace of the pairs given + upload + launch + download. The
+ * device buffers are taken for the call from the context's pool. pairs[2 * n_pairs], dist[n_pairs],
+ * ops[n_pairs * band]. */
+int nmz_ed_align_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
+                       const uint32_t *pairs, uint64_t n_pairs, uint32_t band, uint32_t *dist, nmz_edit_op *ops);
 
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),

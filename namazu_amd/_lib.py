@@ -71,6 +71,11 @@ assert ORDER_PAIR_DTYPE.itemsize == 32
 PAIR_COUNTS_DTYPE = np.dtype([("n_fail_with", "<u4"), ("n_pass_with", "<u4")])
 CONTRAST_INFO_DTYPE = np.dtype([("n_fail", "<u4"), ("n_pass", "<u4"), ("n_positive", "<u8")])
 NMZ_CONTRAST_MAX_RUNS = 65535
+# one op of an edit script (nmz_edit_op) and its kinds
+EDIT_OP_DTYPE = np.dtype([("a_pos", "<u4"), ("b_pos", "<u4"), ("kind", "<u4")])
+assert EDIT_OP_DTYPE.itemsize == 12
+NMZ_EDIT_SUB, NMZ_EDIT_DEL, NMZ_EDIT_INS = 0, 1, 2
+NMZ_ALIGN_MAX_BAND = 64
 
 
 class NmzLibraryError(RuntimeError):
@@ -155,6 +160,12 @@ SIGNATURES = {
     "nmz_ed_plan_counters": (_int, [_P, _P, _P]),
     "nmz_debug_tp_offsets": (_int, [_P, _P, _u32, _u32, _P, _P, _P, _P]),
     "nmz_ed_plan_query_knn": (_int, [_P, _P, _P, _u32, _u32, _P, _P]),
+    "nmz_ed_align_host": (_int, [_P, _u64, _P, _u64, _u32, _P, _P]),
+    "nmz_ed_align_plan_create": (_int, [_P, _u32, _u64, ctypes.POINTER(_P)]),
+    "nmz_ed_align_plan_destroy": (_int, [_P]),
+    "nmz_ed_align_plan_info": (_int, [_P, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
+    "nmz_ed_align_pairs_dev": (_int, [_P, _P, _P, _P, _u64, _P, _P, _P]),
+    "nmz_ed_align_pairs": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P]),
     "nmz_replayable_delivery_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
     "nmz_replayable_delivery_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),
     "nmz_replayable_delivery_plan_destroy": (_int, [_P]),

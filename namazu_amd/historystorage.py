@@ -235,6 +235,19 @@ class Naive(HistoryStorage):
     def AllPairsKNN(self, k, band):
         return allpairs_knn(self.load_all(), k, band)
 
+    def DiffSimilar(self, trace, k, band):
+        """SearchSimilar, then what differs: [(id, distance, script)] for the neighbours within the band, script the
+        ops (EDIT_OP_DTYPE rows) that turn the stored run `id` into `trace` -- one edit_scripts call for all of them.
+        script_moves(stored, trace, script) names the events delivered earlier or later."""
+        t = trace.symbols if isinstance(trace, SingleTrace) else np.asarray(trace, np.uint64)
+        near = [(i, d) for i, d in self.SearchSimilar(trace, k, band) if d <= band]
+        if not near:
+            return []
+        ts = TraceSet([self._index.ts.trace(i) for i, _ in near] + [t])
+        pairs = np.array([[r, len(near)] for r in range(len(near))], np.uint32)
+        es = edit_scripts(ts, pairs, band, ctx=self._index.ctx)
+        return [(i, d, es.script(r).copy()) for r, (i, d) in enumerate(near)]
+
     # ---- order contrast ----------------------------------------------------------
     def OrderContrast(self, sym, arrival_ns, k=64, want_counts=False, ctx=None):
         """The event pairs whose order separates this storage's failing runs from its passing ones
@@ -649,3 +662,100 @@ def order_pair(pos, failed, before, after):
     _lib.check(_lib.load().nmz_order_contrast_host(_lib.ptr(pos), _lib.ptr(failed), R, E, int(before), int(after),
                                                    _lib.ptr(out), _lib.ptr(info)))
     return out[0], int(info[0]["n_fail"]), int(info[0]["n_pass"])
+
+
+# ---- edit scripts: what differs between two traces ------------------------------------------------------------
+class EditScripts:
+    """edit_scripts' result: dist[P] (uint32, ED_band: band + 1 = beyond the band) and ops[P][band] (EDIT_OP_DTYPE:
+    a_pos, b_pos, kind; the pair's ops in forward order, then {NMZ_NONE, NMZ_NONE, NMZ_NONE})."""
+
+    def __init__(self, dist, ops, band):
+        self.dist = dist
+        self.ops = ops
+        self.band = band
+
+    def script(self, p):
+        """The ops of pair p (a view of its first dist[p] rows), or None beyond the band."""
+        d = int(self.dist[p])
+        return self.ops[p, :d] if d <= self.band else None
+
+
+class AlignPlan:
+    """The history scratch of the edit-script kernel for `slots` pairs in flight of up to max_len elements each
+    (nmz_ed_align_plan): pairs_dev aligns device pairs over a device CSR into device dist / ops arrays."""
+
+    def __init__(self, band, max_len, ctx=None):
+        self.ctx = ctx or _lib.default_context()
+        self.band = int(band)
+        self.plan = ctypes.c_void_p()
+        L = _lib.load()
+        _lib.check(L.nmz_ed_align_plan_create(self.ctx.handle, self.band, int(max_len), ctypes.byref(self.plan)))
+        s, h = ctypes.c_uint32(), ctypes.c_uint64()
+        _lib.check(L.nmz_ed_align_plan_info(self.plan, ctypes.byref(s), ctypes.byref(h)))
+        self.slots, self.history_bytes = s.value, h.value
+
+    def pairs_dev(self, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops, stream=None):
+        """Device pointers (ints): uint64 offsets and symbols, uint32 pairs[n_pairs][2] in; uint32 dist[n_pairs]
+        and EDIT_OP_DTYPE ops[n_pairs][band] out, enqueued on `stream` (a HIP stream handle; None = the context's).
+        A pair with a trace longer than max_len gets dist = NMZ_NONE."""
+        _lib.check(_lib.load().nmz_ed_align_pairs_dev(
+            self.plan, ctypes.c_void_p(d_off), ctypes.c_void_p(d_sym), ctypes.c_void_p(d_pairs), int(n_pairs),
+            ctypes.c_void_p(d_dist), ctypes.c_void_p(d_ops), ctypes.c_void_p(stream) if stream else None))
+
+    def close(self):
+        if self.plan:
+            _lib.load().nmz_ed_align_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def edit_scripts(ts, pairs, band, ctx=None):
+    """The canonical edit script of every pair (ia, ib): how trace ia becomes trace ib (nmz_ed_align_pairs; the
+    semantics in include/nmz_gpu.h and DESIGN.md section 2). dist equals ed_pairs' value; band <= 64."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = int(band)
+    if not 0 <= band < 2**32:
+        raise ValueError(f"band = {band} does not fit uint32")
+    dist = np.zeros(len(pairs), np.uint32)
+    ops = np.zeros((len(pairs), min(band, _lib.NMZ_ALIGN_MAX_BAND)), _lib.EDIT_OP_DTYPE)
+    ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_MAX_BAND else None)
+    _lib.check(_lib.load().nmz_ed_align_pairs(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym), len(ts),
+                                              _lib.ptr(pairs), len(pairs), band, _lib.ptr(dist),
+                                              _lib.ptr(ops) if ops.size else None))
+    return EditScripts(dist, ops, band)
+
+
+def edit_script_host(a, b, band):
+    """One pair on the host through nmz_ed_align_host (no GPU): (dist, script) with script the first dist ops, or
+    None beyond the band. A plain banded matrix and the walk by the definition; shares nothing with the kernel."""
+    a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+    b = np.ascontiguousarray(b, np.uint64).reshape(-1)
+    band = int(band)
+    if not 0 <= band < 2**32:
+        raise ValueError(f"band = {band} does not fit uint32")
+    dist = ctypes.c_uint32()
+    ops = np.zeros(min(band, _lib.NMZ_ALIGN_MAX_BAND), _lib.EDIT_OP_DTYPE)
+    _lib.check(_lib.load().nmz_ed_align_host(_lib.ptr(a), len(a), _lib.ptr(b), len(b), band, ctypes.byref(dist),
+                                             _lib.ptr(ops) if ops.size else None))
+    return dist.value, (ops[:dist.value] if dist.value <= band else None)
+
+
+def script_moves(a, b, ops):
+    """The events a script moved: the k-th DEL of a symbol value pairs with the k-th INS of that value, in script
+    order. Returns [(symbol, a_pos, b_pos)]: a[a_pos] was delivered at b_pos of b instead. DELs and INSs without a
+    partner (an event missing or extra) and SUBs are not moves."""
+    dels, inss = {}, {}
+    for o in ops:
+        k = int(o["kind"])
+        if k == _lib.NMZ_EDIT_DEL:
+            dels.setdefault(int(a[int(o["a_pos"])]), []).append(int(o["a_pos"]))
+        elif k == _lib.NMZ_EDIT_INS:
+            inss.setdefault(int(b[int(o["b_pos"])]), []).append(int(o["b_pos"]))
+    out = [(s, ap, bp) for s, aps in dels.items() for ap, bp in zip(aps, inss.get(s, []))]
+    return sorted(out, key=lambda t: (t[1], t[2]))
+

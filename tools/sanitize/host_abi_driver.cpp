@@ -312,6 +312,102 @@ static void match_cases() {
     CHECK(nmz_match_runs_dev(nullptr, off, run, 2, rows, nullptr) == NMZ_EINVAL);
 }
 
+// the edit script's host form: the known answers of DESIGN.md section 2 ("Edit scripts"), empty traces, band 0, 64
+// and 65, every refusal, and the device forms' NULL plan and context
+static std::vector<uint64_t> syms(const char *s) {
+    std::vector<uint64_t> v;
+    for (; *s; ++s) v.push_back(0x9E3779B97F4A7C15ull * (uint64_t)(unsigned char)*s + 5);
+    return v;
+}
+
+static bool script_is(const char *a, const char *b, uint32_t band, uint32_t want_dist,
+                      std::vector<nmz_edit_op> want) {
+    const std::vector<uint64_t> va = syms(a), vb = syms(b);
+    std::vector<nmz_edit_op> ops(band ? band : 1, nmz_edit_op{7, 7, 7});
+    uint32_t dist = 99;
+    nmz_edit_op *po = band ? ops.data() : nullptr;
+    if (nmz_ed_align_host(va.data(), va.size(), vb.data(), vb.size(), band, &dist, po) != NMZ_OK) return false;
+    if (dist != want_dist) return false;
+    want.resize(band, nmz_edit_op{NMZ_NONE, NMZ_NONE, NMZ_NONE});
+    for (uint32_t s = 0; s < band; ++s)
+        if (ops[s].a_pos != want[s].a_pos || ops[s].b_pos != want[s].b_pos || ops[s].kind != want[s].kind) return false;
+    return true;
+}
+
+static void align_cases() {
+    const uint32_t S = NMZ_EDIT_SUB, D = NMZ_EDIT_DEL, I = NMZ_EDIT_INS;
+    CHECK(script_is("kitten", "sitting", 3, 3, {{0, 0, S}, {4, 4, S}, {6, 6, I}}));
+    CHECK(script_is("kitten", "sitting", 2, 3, {}));
+    CHECK(script_is("abc", "", 3, 3, {{0, 0, D}, {1, 0, D}, {2, 0, D}}));
+    CHECK(script_is("", "ab", 2, 2, {{0, 0, I}, {0, 1, I}}));
+    CHECK(script_is("ab", "ba", 2, 2, {{0, 0, S}, {1, 1, S}}));
+    CHECK(script_is("aab", "ab", 1, 1, {{0, 0, D}}));
+    CHECK(script_is("ab", "aab", 1, 1, {{0, 0, I}}));
+    CHECK(script_is("abcde", "bcdex", 2, 2, {{0, 0, D}, {5, 4, I}}));
+    CHECK(script_is("abab", "baba", 2, 2, {{0, 0, I}, {3, 4, D}}));
+    CHECK(script_is("aaaa", "aa", 2, 2, {{0, 0, D}, {1, 0, D}}));
+    CHECK(script_is("", "", 4, 0, {}));
+    CHECK(script_is("", "", 0, 0, {}));
+    CHECK(script_is("abc", "abc", 0, 0, {}));
+    CHECK(script_is("abc", "abd", 0, 1, {}));
+    CHECK(script_is("abc", "ab", 0, 1, {}));
+    // band 64: 64 deletions at the band's edge, then one more than the band holds; band 65 is refused
+    std::vector<uint64_t> a(200), b;
+    for (size_t i = 0; i < a.size(); ++i) a[i] = 1000 + i;
+    b.assign(a.begin() + 64, a.end());
+    std::vector<nmz_edit_op> ops(65);
+    uint32_t dist = 0;
+    CHECK(nmz_ed_align_host(a.data(), a.size(), b.data(), b.size(), 64, &dist, ops.data()) == NMZ_OK && dist == 64);
+    for (uint32_t s = 0; s < 64; ++s) CHECK(ops[s].a_pos == s && ops[s].b_pos == 0 && ops[s].kind == D);
+    CHECK(nmz_ed_align_host(b.data(), b.size(), a.data(), a.size(), 64, &dist, ops.data()) == NMZ_OK && dist == 64);
+    for (uint32_t s = 0; s < 64; ++s) CHECK(ops[s].a_pos == 0 && ops[s].b_pos == s && ops[s].kind == I);
+    CHECK(nmz_ed_align_host(a.data(), a.size(), b.data() + 1, b.size() - 1, 64, &dist, ops.data()) == NMZ_OK);
+    CHECK(dist == 65 && ops[0].kind == NMZ_NONE && ops[63].a_pos == NMZ_NONE);
+    CHECK(nmz_ed_align_host(a.data(), a.size(), b.data(), b.size(), 65, &dist, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "NMZ_ALIGN_MAX_BAND") != nullptr);
+    CHECK(nmz_ed_align_host(a.data(), 0xFFFFFFFFull, b.data(), 3, 4, &dist, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "at most 2^32 - 2") != nullptr);
+    CHECK(nmz_ed_align_host(a.data(), 3, b.data(), 0xFFFFFFFFull, 4, &dist, ops.data()) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_host(nullptr, 3, b.data(), 3, 4, &dist, ops.data()) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_host(a.data(), 3, nullptr, 3, 4, &dist, ops.data()) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_host(a.data(), 3, b.data(), 3, 4, nullptr, ops.data()) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_host(a.data(), 3, b.data(), 3, 4, &dist, nullptr) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ops is NULL") != nullptr);
+    CHECK(nmz_ed_align_host(nullptr, 0, nullptr, 0, 0, &dist, nullptr) == NMZ_OK && dist == 0);
+    // the host-pointer form: every refusal comes before the context is looked at
+    const uint64_t off[4] = {0, 3, 3, 8}, dec[4] = {0, 5, 3, 8}, big[3] = {0, 0xFFFFFFFFull, 0x100000000ull};
+    const uint32_t pairs[4] = {0, 2, 1, 1}, bad[2] = {0, 3};
+    uint32_t d2[2];
+    CHECK(nmz_ed_align_pairs(nullptr, off, a.data(), 3, pairs, 2, 8, d2, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    CHECK(nmz_ed_align_pairs(nullptr, off, a.data(), 3, pairs, 2, 65, d2, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "wider bands") != nullptr);
+    CHECK(nmz_ed_align_pairs(nullptr, off, a.data(), 3, bad, 1, 8, d2, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "pair index out of range") != nullptr);
+    CHECK(nmz_ed_align_pairs(nullptr, dec, a.data(), 3, pairs, 2, 8, d2, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "non-decreasing") != nullptr);
+    CHECK(nmz_ed_align_pairs(nullptr, big, a.data(), 2, pairs + 2, 1, 8, d2, ops.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "trace 0 has 4294967295 elements") != nullptr);
+    CHECK(nmz_ed_align_pairs(nullptr, off, a.data(), 3, pairs, 2, 8, nullptr, ops.data()) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_pairs(nullptr, off, a.data(), 3, pairs, 2, 8, d2, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_pairs(nullptr, nullptr, nullptr, 0, nullptr, 0, 8, nullptr, nullptr) == NMZ_OK);
+    CHECK(nmz_ed_align_pairs(nullptr, nullptr, nullptr, 0, nullptr, 0, 65, nullptr, nullptr) == NMZ_EINVAL);
+    // the plan and the device form
+    nmz_ed_align_plan *plan = reinterpret_cast<nmz_ed_align_plan *>(0x1);
+    CHECK(nmz_ed_align_plan_create(nullptr, 8, 100, &plan) == NMZ_EINVAL && plan == nullptr);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    CHECK(nmz_ed_align_plan_create(nullptr, 65, 100, &plan) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "NMZ_ALIGN_MAX_BAND") != nullptr);
+    CHECK(nmz_ed_align_plan_create(nullptr, 64, 1ull << 30, &plan) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "max_len 1073741824") != nullptr && std::strstr(nmz_last_error(), "budget"));
+    CHECK(nmz_ed_align_plan_create(nullptr, 8, 0xFFFFFFFFull, &plan) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_plan_create(nullptr, 8, 100, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_plan_destroy(nullptr) == NMZ_OK);
+    CHECK(nmz_ed_align_plan_info(nullptr, nullptr, nullptr) == NMZ_EINVAL);
+    CHECK(nmz_ed_align_pairs_dev(nullptr, off, a.data(), pairs, 2, d2, ops.data(), nullptr) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "plan is NULL") != nullptr);
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -362,6 +458,7 @@ int main() {
     order_cases();
     delivery_cases();
     match_cases();
+    align_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
