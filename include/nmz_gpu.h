@@ -37,6 +37,9 @@
  *   nmz_ed_align_*         -> the same interface, extended: the edit script between
  *                             two traces (which events moved, are missing or were
  *                             replaced); an empty script <=> SingleTrace.Equals.
+ *   nmz_script_moves_host / nmz_move_profile* / nmz_ed_diff_profile -> the same
+ *                             interface once more: the scripts of many pairs tallied per
+ *                             event symbol (delivered later, earlier, dropped, extra).
  *
  * Buffers passed to the host-pointer entry points are borrowed for the call
  * only and never retained (cgo pointer rules). The *_dev entry points take
@@ -964,6 +967,82 @@ int nmz_ed_align_pairs_dev(nmz_ed_align_plan *plan, const uint64_t *d_off, const
  * ops[n_pairs * band]. */
 int nmz_ed_align_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
                        const uint32_t *pairs, uint64_t n_pairs, uint32_t band, uint32_t *dist, nmz_edit_op *ops);
+
+/* ---- move profiles: which events move between the runs of many pairs ----------------------------------------
+ * A build-defined extension of the same optional interface (historystorage/historystorage.go:50-51; the reference has
+ * equality only, naive/naive.go:235-257; the labels of failing and passing runs naive.go:199-213). Input: the scripts
+ * nmz_ed_align_* gives, `band` slots per pair and dist per pair. A pair with dist <= band is a *script* of dist ops
+ * o_0 .. o_{dist-1}; every other pair (dist == band + 1, dist == NMZ_NONE) is *beyond* and contributes nothing.
+ *   Names.    A DEL names a[a_pos]. An INS names b[b_pos]. A SUB names a[a_pos] (from) and b[b_pos] (to).
+ *   Partners. The r-th DEL naming value v (r from 0, script order) and the r-th INS naming v are partners: a *move*
+ *             of v. partner[s] is the partner's slot index; NMZ_NONE for a DEL or INS without a partner, for every
+ *             SUB, for sentinel slots and for every slot of a pair beyond the band.
+ *   Direction. A move is *later* when its INS slot comes after its DEL slot (in b the event is delivered later than
+ *             in a), else *earlier*; slots are strictly ordered, so there is no tie.
+ *             span = |ops[ins].b_pos - ops[del].b_pos|.
+ *   Profile.  usym[n_usym]: the symbols to tally, strictly increasing; n_usym == 0 is legal. counts[n_usym], one
+ *             nmz_move_counts per table symbol; a name that is not in the table is skipped in the counters (it
+ *             counts in info.n_unknown) but still pairs up in `partner`.
+ * Limits of the host-pointer forms, each NMZ_EINVAL with a message, checked before any device work (arguments before
+ * the context): everything nmz_ed_align_pairs checks, with its messages; usym strictly increasing;
+ * n_pairs * band < 2^32 (no uint32 counter can wrap); where ops are an input, for the first dist slots of every
+ * script: kind <= 2, a_pos < n for DEL / SUB, b_pos < m for INS / SUB. n_pairs == 0 is legal and needs no device:
+ * the counters and the info are zero. */
+typedef struct nmz_move_counts {
+    uint32_t later;        /* moves of the symbol whose INS slot follows its DEL slot                     */
+    uint32_t earlier;      /* moves of the symbol whose INS slot precedes its DEL slot                    */
+    uint32_t dropped;      /* DELs of the symbol without a partner                                        */
+    uint32_t extra;        /* INSs of the symbol without a partner                                        */
+    uint32_t sub_from;     /* SUBs that name the symbol as a[a_pos]                                       */
+    uint32_t sub_to;       /* SUBs that name the symbol as b[b_pos]                                       */
+    uint32_t n_pairs;      /* scripts in which at least one op names the symbol (once per script)         */
+    uint32_t reserved;     /* always 0                                                                    */
+    uint64_t span_later;   /* sum of span over the symbol's later moves                                   */
+    uint64_t span_earlier; /* sum of span over the symbol's earlier moves                                 */
+} nmz_move_counts;
+typedef struct nmz_move_info {
+    uint64_t n_scripts; /* pairs with dist <= band                                                        */
+    uint64_t n_beyond;  /* all other pairs                                                                */
+    uint64_t n_ops;     /* sum of dist over the scripts                                                   */
+    uint64_t n_unknown; /* names of ops that are not in the table (a SUB can add 2)                       */
+} nmz_move_info;
+/* One script on the calling host thread, no device work (historystorage.go:50-51, naive.go:235-257): partner[n_ops]
+ * by the definition -- plain loops and a std::map of per-value queues. It shares nothing with the kernel: the form
+ * to vet a result with. Every op is live: kind <= 2 and the positions it reads inside a / b, else NMZ_EINVAL. */
+int nmz_script_moves_host(const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m, const nmz_edit_op *ops,
+                          uint32_t n_ops, uint32_t *partner /* [n_ops] */);
+/* The whole profile on the calling host thread, plain loops, no device work (historystorage.go:50-51,
+ * naive.go:199-213, 235-257): for callers without a device, and the check of the device forms. dist[n_pairs] and
+ * ops[n_pairs * band] as nmz_ed_align_pairs writes them; partner[n_pairs * band] may be NULL. */
+int nmz_move_profile_host(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                          uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
+                          const uint64_t *usym, uint64_t n_usym, uint32_t *partner /* may be NULL */,
+                          nmz_move_counts *counts /* [n_usym] */, nmz_move_info *info);
+/* Device pointers in and out (historystorage.go:50-51, naive.go:199-213, 235-257); enqueued on `stream` (NULL = the
+ * context's). accumulate == 0: d_counts[n_usym] and d_info are cleared on that stream first; accumulate != 0: the
+ * call adds to them, so the batches of one job sum. Apart from the clear it enqueues one launch and allocates
+ * nothing. The host cannot read the inputs: band <= NMZ_ALIGN_MAX_BAND, n_pairs * band < 2^32 and d_usym strictly
+ * increasing are the caller's to keep, offsets and pairs as for nmz_ed_align_pairs_dev; an op of a script with
+ * kind > 2 or a position outside its trace counts for nothing (no name, no partner), and the kernel makes no
+ * out-of-range read for it. d_partner[n_pairs * band] may be NULL. */
+int nmz_move_profile_dev(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_pairs,
+                         uint64_t n_pairs, uint32_t band, const uint32_t *d_dist, const nmz_edit_op *d_ops,
+                         const uint64_t *d_usym, uint64_t n_usym, uint32_t *d_partner /* may be NULL */,
+                         nmz_move_counts *d_counts, nmz_move_info *d_info, int accumulate, void *stream);
+/* Host pointers, synchronous, built on the _dev form (historystorage.go:50-51, naive.go:199-213, 235-257): the
+ * scripts are given; upload + launch + download. The device buffers are taken for the call from the context's
+ * pool. partner may be NULL. */
+int nmz_move_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                     uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
+                     const uint64_t *usym, uint64_t n_usym, uint32_t *partner /* may be NULL */,
+                     nmz_move_counts *counts, nmz_move_info *info);
+/* From the traces to the profile (historystorage.go:50-51, naive.go:199-213, 235-257): the CSR goes up, the pairs
+ * are aligned (k_ed_align) and profiled on the device; only dist (may be NULL), counts and info come back, the ops
+ * never leave the device. Plan and buffers are taken for the call from the context's pool, as nmz_ed_align_pairs
+ * takes them. The result is byte-identical to nmz_move_profile over nmz_ed_align_pairs' output. */
+int nmz_ed_diff_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
+                        const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint64_t *usym, uint64_t n_usym,
+                        uint32_t *dist /* may be NULL */, nmz_move_counts *counts, nmz_move_info *info);
 
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),

@@ -76,6 +76,13 @@ EDIT_OP_DTYPE = np.dtype([("a_pos", "<u4"), ("b_pos", "<u4"), ("kind", "<u4")])
 assert EDIT_OP_DTYPE.itemsize == 12
 NMZ_EDIT_SUB, NMZ_EDIT_DEL, NMZ_EDIT_INS = 0, 1, 2
 NMZ_ALIGN_MAX_BAND = 64
+# move profiles: one table symbol's counters (nmz_move_counts) and the call's totals (nmz_move_info)
+MOVE_COUNTS_DTYPE = np.dtype([("later", "<u4"), ("earlier", "<u4"), ("dropped", "<u4"), ("extra", "<u4"),
+                              ("sub_from", "<u4"), ("sub_to", "<u4"), ("n_pairs", "<u4"), ("reserved", "<u4"),
+                              ("span_later", "<u8"), ("span_earlier", "<u8")])
+assert MOVE_COUNTS_DTYPE.itemsize == 48
+MOVE_INFO_DTYPE = np.dtype([("n_scripts", "<u8"), ("n_beyond", "<u8"), ("n_ops", "<u8"), ("n_unknown", "<u8")])
+assert MOVE_INFO_DTYPE.itemsize == 32
 
 
 class NmzLibraryError(RuntimeError):
@@ -166,6 +173,11 @@ SIGNATURES = {
     "nmz_ed_align_plan_info": (_int, [_P, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
     "nmz_ed_align_pairs_dev": (_int, [_P, _P, _P, _P, _u64, _P, _P, _P]),
     "nmz_ed_align_pairs": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P]),
+    "nmz_script_moves_host": (_int, [_P, _u64, _P, _u64, _P, _u32, _P]),
+    "nmz_move_profile_host": (_int, [_P, _P, _u32, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P]),
+    "nmz_move_profile_dev": (_int, [_P, _P, _P, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P, _int, _P]),
+    "nmz_move_profile": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P]),
+    "nmz_ed_diff_profile": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _u64, _P, _P, _P]),
     "nmz_replayable_delivery_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
     "nmz_replayable_delivery_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),
     "nmz_replayable_delivery_plan_destroy": (_int, [_P]),

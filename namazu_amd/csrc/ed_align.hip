@@ -254,7 +254,7 @@ struct nmz_ed_align_plan {
 
 namespace nmz {
 
-static int align_band(uint32_t band) {
+int align_band(uint32_t band) {
     NMZ_CHECK(band <= NMZ_ALIGN_MAX_BAND, "band " + std::to_string(band) +
                                               " exceeds NMZ_ALIGN_MAX_BAND (64): edit scripts over wider bands are "
                                               "not built yet");
@@ -267,9 +267,8 @@ static int align_len(const std::string &what, uint64_t len) {
 }
 
 // every limit of nmz_ed_align_pairs, no device; *max_len = the longest trace of the pairs
-static int align_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
-                          uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
-                          uint64_t *max_len) {
+int align_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                   uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, uint64_t *max_len) {
     NMZ_TRY(align_band(band));
     *max_len = 0;
     if (n_pairs == 0) return NMZ_OK;
@@ -289,7 +288,7 @@ static int align_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_t
 }
 
 // the plan's shape for (band, max_len): no device
-static int align_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
+int align_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
     NMZ_TRY(align_band(band));
     NMZ_TRY(align_len("a trace of max_len", max_len));
     *slot_words = al_blocks(max_len) * 2 * al_cells(band) * 64;
@@ -299,7 +298,7 @@ static int align_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
     return NMZ_OK;
 }
 
-static void align_plan_destroy_locked(nmz_ed_align_plan *p) {
+void align_plan_destroy_locked(nmz_ed_align_plan *p) {
     if (p->ev) {
         (void)hipEventSynchronize(p->ev);
         (void)hipEventDestroy(p->ev);
@@ -308,8 +307,8 @@ static void align_plan_destroy_locked(nmz_ed_align_plan *p) {
     delete p;
 }
 
-static int align_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_t slot_words,
-                                    nmz_ed_align_plan **out) {
+int align_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_t slot_words,
+                             nmz_ed_align_plan **out) {
     auto *p = new nmz_ed_align_plan();
     p->ctx = ctx;
     p->band = band;
@@ -330,8 +329,8 @@ static int align_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_le
     return NMZ_OK;
 }
 
-static int align_enqueue(nmz_ed_align_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
-                         const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops) {
+int align_enqueue(nmz_ed_align_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
+                  const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops) {
     NMZ_CHECK(n_pairs <= (SIZE_MAX / sizeof(nmz_edit_op)) / NMZ_ALIGN_MAX_BAND,
               "n_pairs * band does not fit the output");
     if (n_pairs == 0) return NMZ_OK;
@@ -355,19 +354,11 @@ static int align_enqueue(nmz_ed_align_plan *p, hipStream_t st, const uint64_t *d
     return rc;
 }
 
-// One host-form call on the context's stream; the caller holds ctx and has validated. The destructor drains the
-// stream before plan and buffers go back to the pool.
-struct AlignCall {
-    nmz_ctx *ctx;
-    nmz_ed_align_plan *plan = nullptr;
-    DevBuf work;
-    explicit AlignCall(nmz_ctx *c) : ctx(c) { work.pool = &c->pool; }
-    ~AlignCall() {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (plan) align_plan_destroy_locked(plan);
-        work.release();
-    }
-};
+AlignCall::~AlignCall() {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (plan) align_plan_destroy_locked(plan);
+    work.release();
+}
 
 }  // namespace nmz
 

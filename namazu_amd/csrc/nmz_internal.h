@@ -49,4 +49,26 @@ struct MatchCall {
             const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos);
 };
 
+// ed_align.hip, for ed_moves.hip (nmz_move_profile, nmz_ed_diff_profile). align_validate: every limit of
+// nmz_ed_align_pairs, no device; *max_len = the longest trace of the pairs. align_shape: the plan's shape for
+// (band, max_len), no device. The _locked forms and align_enqueue want the caller to hold the context.
+int align_band(uint32_t band);
+int align_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                   uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, uint64_t *max_len);
+int align_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words);
+int align_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_t slot_words,
+                             nmz_ed_align_plan **out);
+void align_plan_destroy_locked(nmz_ed_align_plan *p);
+int align_enqueue(nmz_ed_align_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
+                  const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops);
+// One host-form call on the context's stream; the caller holds ctx and has validated. The destructor drains the
+// stream before plan and buffers go back to the pool.
+struct AlignCall {
+    nmz_ctx *ctx;
+    nmz_ed_align_plan *plan = nullptr;
+    DevBuf work;
+    explicit AlignCall(nmz_ctx *c) : ctx(c) { work.pool = &c->pool; }
+    ~AlignCall();
+};
+
 }  // namespace nmz

@@ -248,6 +248,40 @@ class Naive(HistoryStorage):
         es = edit_scripts(ts, pairs, band, ctx=self._index.ctx)
         return [(i, d, es.script(r).copy()) for r, (i, d) in enumerate(near)]
 
+    def DiffFailing(self, band, k=1, ctx=None):
+        """Which events are delivered later, earlier, dropped or extra in this storage's failing runs, each measured
+        against its k nearest passing runs (move_profile). The runs are loaded and labelled as OrderContrast does it
+        (IsSuccessful, naive.go:199-213; a run whose result cannot be read is skipped, cli/tools/summary.go:47-51). A
+        SimilarityIndex over the passing runs answers the failing runs' queries; the pairs are (a = passing
+        neighbour, b = failing run) for the neighbours within the band, so "later" reads "delivered later in the
+        failing run". Returns the MoveProfile of one move_profile call, its .pairs the stored-run ids behind the
+        pairs; .top(k) ranks the symbols."""
+        passing, failing = [], []
+        for i in range(self.NrStoredHistories()):
+            ok, err = self.IsSuccessful(i)
+            if err is not None:
+                continue
+            t, err = self.GetStoredHistory(i)
+            if err is not None:
+                raise RuntimeError(f"failed to get history {i}: {err}")  # naive.go:241 panics
+            (passing if ok else failing).append((i, t.symbols))
+        if not failing:
+            raise ValueError("no failing run: nothing to contrast")
+        if not passing:
+            raise ValueError("no passing run: nothing to contrast")
+        index = SimilarityIndex(TraceSet([t for _, t in passing]), band, ctx=ctx)
+        try:
+            ids, ds = index.query([t for _, t in failing], int(k))
+        finally:
+            index.close()
+        near = [(int(j), f) for f in range(len(failing)) for j, d in zip(ids[f], ds[f])
+                if j != _lib.NMZ_NONE and d <= band]
+        ts = TraceSet([t for _, t in passing] + [t for _, t in failing])
+        pairs = np.array([[j, len(passing) + f] for j, f in near], np.uint32).reshape(-1, 2)
+        prof = move_profile(ts, pairs, band, ctx=index.ctx)
+        prof.pairs = np.array([[passing[j][0], failing[f][0]] for j, f in near], np.uint32).reshape(-1, 2)
+        return prof
+
     # ---- order contrast ----------------------------------------------------------
     def OrderContrast(self, sym, arrival_ns, k=64, want_counts=False, ctx=None):
         """The event pairs whose order separates this storage's failing runs from its passing ones
@@ -759,3 +793,101 @@ def script_moves(a, b, ops):
     out = [(s, ap, bp) for s, aps in dels.items() for ap, bp in zip(aps, inss.get(s, []))]
     return sorted(out, key=lambda t: (t[1], t[2]))
 
+
+
+# ---- move profiles: which events move between the runs of many pairs ----------------------------------------------
+def script_partners(a, b, ops):
+    """script_moves' pairing as slot indices, on the host through nmz_script_moves_host (no GPU): partner[len(ops)]
+    (uint32), the slot of the INS that the DEL of slot s pairs with and the other way round -- the r-th DEL naming a
+    value and the r-th INS naming it, in script order -- and NMZ_NONE for a DEL or INS without a partner and for
+    every SUB. Plain loops by the definition; shares nothing with the kernel."""
+    a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+    b = np.ascontiguousarray(b, np.uint64).reshape(-1)
+    ops = np.ascontiguousarray(ops, _lib.EDIT_OP_DTYPE).reshape(-1)
+    partner = np.full(len(ops), _lib.NMZ_NONE, np.uint32)
+    _lib.check(_lib.load().nmz_script_moves_host(_lib.ptr(a), len(a), _lib.ptr(b), len(b), _lib.ptr(ops), len(ops),
+                                                 _lib.ptr(partner)))
+    return partner
+
+
+class MoveProfile:
+    """move_profile's result: symbols[U] (uint64, increasing), counts[U] (MOVE_COUNTS_DTYPE: later, earlier, dropped,
+    extra, sub_from, sub_to, n_pairs, span_later, span_earlier of that symbol over all the scripts), info (one
+    MOVE_INFO_DTYPE record: n_scripts, n_beyond, n_ops, n_unknown), dist[P] (ED_band of every pair) and, from
+    move_profile_of on request, partner[P][band]. "Later" = delivered later in b (the pair's second trace) than in
+    a."""
+
+    def __init__(self, symbols, counts, info, dist, partner=None):
+        self.symbols = symbols
+        self.counts = counts
+        self.info = info
+        self.dist = dist
+        self.partner = partner
+        self.pairs = None  # Naive.DiffFailing: the stored-run ids (passing neighbour, failing run) behind the pairs
+
+    def top(self, k):
+        """The k symbols that most scripts name, as [(symbol, counts record)]: by (n_pairs desc, later + earlier
+        desc, symbol asc); symbols no script names are left out."""
+        c = self.counts
+        moved = c["later"].astype(np.int64) + c["earlier"].astype(np.int64)
+        order = np.lexsort((self.symbols, -moved, -c["n_pairs"].astype(np.int64)))
+        return [(int(self.symbols[u]), c[u]) for u in order[:int(k)] if c[u]["n_pairs"] > 0]
+
+
+def _move_table(ts, usym):
+    if usym is None:
+        total = int(ts.off[-1])
+        return np.unique(ts.sym[:total])
+    return np.ascontiguousarray(usym, np.uint64).reshape(-1)
+
+
+def _move_band(band):
+    band = int(band)
+    if not 0 <= band < 2**32:
+        raise ValueError(f"band = {band} does not fit uint32")
+    return band
+
+
+def move_profile(ts, pairs, band, ctx=None, usym=None):
+    """From traces to the tally in one call (nmz_ed_diff_profile; the semantics in include/nmz_gpu.h and DESIGN.md
+    section 2, "Move profiles"): every pair (ia, ib) is aligned as edit_scripts aligns it and its script's ops are
+    paired and counted per symbol on the device; the ops never come to the host. usym: the symbols to tally
+    (strictly increasing; default: every symbol of ts). Returns a MoveProfile; band <= 64."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = _move_band(band)
+    usym = _move_table(ts, usym)
+    dist = np.zeros(len(pairs), np.uint32)
+    counts = np.zeros(len(usym), _lib.MOVE_COUNTS_DTYPE)
+    info = np.zeros(1, _lib.MOVE_INFO_DTYPE)
+    ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_MAX_BAND else None)
+    _lib.check(_lib.load().nmz_ed_diff_profile(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym), len(ts),
+                                               _lib.ptr(pairs), len(pairs), band, _lib.ptr(usym), len(usym),
+                                               _lib.ptr(dist), _lib.ptr(counts) if len(usym) else None,
+                                               _lib.ptr(info)))
+    return MoveProfile(usym, counts, info[0], dist)
+
+
+def move_profile_of(ts, pairs, es, ctx=None, usym=None, want_partner=False, host=False):
+    """The tally of scripts the caller already holds (es: edit_scripts' result over the same ts and pairs), through
+    nmz_move_profile -- or, with host=True, through nmz_move_profile_host on the calling thread (no GPU).
+    want_partner adds partner[P][band] (uint32: the partner's slot, NMZ_NONE without one) to the MoveProfile."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = _move_band(es.band)
+    usym = _move_table(ts, usym)
+    dist = np.ascontiguousarray(es.dist, np.uint32).reshape(-1)
+    ops = np.ascontiguousarray(es.ops, _lib.EDIT_OP_DTYPE)
+    if len(dist) != len(pairs) or ops.shape != (len(pairs), min(band, _lib.NMZ_ALIGN_MAX_BAND)):
+        raise ValueError(f"scripts of shape {ops.shape} for {len(pairs)} pairs at band {band}")
+    counts = np.zeros(len(usym), _lib.MOVE_COUNTS_DTYPE)
+    info = np.zeros(1, _lib.MOVE_INFO_DTYPE)
+    partner = np.full(ops.shape, _lib.NMZ_NONE, np.uint32) if want_partner else None
+    args = (_lib.ptr(ts.off), _lib.ptr(ts.sym), len(ts), _lib.ptr(pairs), len(pairs), band, _lib.ptr(dist),
+            _lib.ptr(ops) if ops.size else None, _lib.ptr(usym), len(usym),
+            _lib.ptr(partner) if want_partner and partner.size else None, _lib.ptr(counts) if len(usym) else None,
+            _lib.ptr(info))
+    if host:
+        _lib.check(_lib.load().nmz_move_profile_host(*args))
+    else:
+        ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_MAX_BAND else None)
+        _lib.check(_lib.load().nmz_move_profile(ctx.handle if ctx else None, *args))
+    return MoveProfile(usym, counts, info[0], dist, partner)

@@ -408,6 +408,103 @@ static void align_cases() {
     CHECK(std::strstr(nmz_last_error(), "plan is NULL") != nullptr);
 }
 
+// the move profile's host forms: the known answers of DESIGN.md section 2 ("Move profiles") through
+// nmz_ed_align_host's scripts, a full band whose last slot has a partner 32 slots away, a table without one symbol,
+// an empty table, no pairs, and the refusals (the device forms' come before the context is looked at)
+static void moves_cases() {
+    const uint32_t D = NMZ_EDIT_DEL, I = NMZ_EDIT_INS, NONE = NMZ_NONE;
+    // abab -> baba, w = 2: INS(0, 0) DEL(3, 4) are partners, b moves earlier over a span of 4
+    const std::vector<uint64_t> ab = syms("abab"), ba = syms("baba");
+    std::vector<uint64_t> sym(ab);
+    sym.insert(sym.end(), ba.begin(), ba.end());
+    const uint64_t off[3] = {0, 4, 8};
+    const uint32_t pairs[4] = {0, 1, 1, 1};
+    uint32_t dist[2] = {9, 9};
+    std::vector<nmz_edit_op> ops(4);
+    for (int p = 0; p < 2; ++p)
+        CHECK(nmz_ed_align_host(sym.data() + off[pairs[2 * p]], 4, sym.data() + off[pairs[2 * p + 1]], 4, 2, &dist[p],
+                                ops.data() + 2 * p) == NMZ_OK);
+    CHECK(dist[0] == 2 && dist[1] == 0 && ops[0].kind == I && ops[1].kind == D);
+    uint32_t pr2[2] = {7, 7};
+    CHECK(nmz_script_moves_host(ab.data(), 4, ba.data(), 4, ops.data(), 2, pr2) == NMZ_OK && pr2[0] == 1 && pr2[1] == 0);
+    uint64_t usym[2] = {syms("a")[0], syms("b")[0]};
+    if (usym[0] > usym[1]) std::swap(usym[0], usym[1]);
+    const int ib = usym[0] == syms("b")[0] ? 0 : 1;
+    nmz_move_counts counts[2];
+    nmz_move_info info;
+    uint32_t partner[4] = {7, 7, 7, 7};
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 2, 2, dist, ops.data(), usym, 2, partner, counts, &info) ==
+          NMZ_OK);
+    CHECK(partner[0] == 1 && partner[1] == 0 && partner[2] == NONE && partner[3] == NONE);
+    CHECK(info.n_scripts == 2 && info.n_beyond == 0 && info.n_ops == 2 && info.n_unknown == 0);
+    CHECK(counts[ib].earlier == 1 && counts[ib].span_earlier == 4 && counts[ib].n_pairs == 1 && counts[ib].later == 0);
+    CHECK(counts[1 - ib].n_pairs == 0 && counts[1 - ib].earlier == 0 && counts[ib].reserved == 0);
+    // the table without b, then no table: the names are unknown, the partners stay
+    const uint64_t only_a = syms("a")[0];
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 2, 2, dist, ops.data(), &only_a, 1, partner, counts, &info) ==
+          NMZ_OK);
+    CHECK(info.n_unknown == 2 && counts[0].n_pairs == 0 && partner[0] == 1 && partner[1] == 0);
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 2, 2, dist, ops.data(), nullptr, 0, nullptr, nullptr, &info) ==
+          NMZ_OK);
+    CHECK(info.n_unknown == 2 && info.n_ops == 2);
+    // X^32 + B -> B + X^32, w = 64: 32 DELs, then 32 INSs, partner[s] = s + 32, all later
+    std::vector<uint64_t> a, b;
+    for (int r = 0; r < 32; ++r) a.push_back(5000);
+    for (int t = 0; t < 66; ++t) a.push_back(100 + t), b.push_back(100 + t);
+    for (int r = 0; r < 32; ++r) b.push_back(5000);
+    std::vector<nmz_edit_op> o64(64);
+    std::vector<uint32_t> p64(64, 7);
+    uint32_t d64 = 0;
+    CHECK(nmz_ed_align_host(a.data(), a.size(), b.data(), b.size(), 64, &d64, o64.data()) == NMZ_OK && d64 == 64);
+    CHECK(nmz_script_moves_host(a.data(), a.size(), b.data(), b.size(), o64.data(), 64, p64.data()) == NMZ_OK);
+    for (uint32_t s = 0; s < 32; ++s) CHECK(o64[s].kind == D && p64[s] == s + 32 && p64[s + 32] == s);
+    std::vector<uint64_t> both(a);
+    both.insert(both.end(), b.begin(), b.end());
+    const uint64_t off2[3] = {0, a.size(), a.size() + b.size()}, x = 5000;
+    const uint32_t fwd[2] = {0, 1};
+    nmz_move_counts cx;
+    CHECK(nmz_move_profile_host(off2, both.data(), 2, fwd, 1, 64, &d64, o64.data(), &x, 1, p64.data(), &cx, &info) ==
+          NMZ_OK);
+    CHECK(cx.later == 32 && cx.earlier == 0 && cx.n_pairs == 1 && cx.span_later == 32 * 66 + 496 && p64[63] == 31);
+    // no pairs: zeros, from every form, without a device
+    cx.later = 7;
+    info.n_ops = 7;
+    CHECK(nmz_move_profile_host(nullptr, nullptr, 0, nullptr, 0, 8, nullptr, nullptr, &x, 1, nullptr, &cx, &info) == NMZ_OK);
+    CHECK(cx.later == 0 && info.n_ops == 0);
+    cx.later = 7;
+    CHECK(nmz_move_profile(nullptr, nullptr, nullptr, 0, nullptr, 0, 8, nullptr, nullptr, &x, 1, nullptr, &cx, &info) ==
+          NMZ_OK && cx.later == 0);
+    cx.later = 7;
+    CHECK(nmz_ed_diff_profile(nullptr, nullptr, nullptr, 0, nullptr, 0, 8, &x, 1, nullptr, &cx, &info) == NMZ_OK &&
+          cx.later == 0);
+    // refusals
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 2, 65, dist, ops.data(), usym, 2, partner, counts, &info) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "wider bands") != nullptr);
+    const uint64_t same[2] = {usym[0], usym[0]};
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 2, 2, dist, ops.data(), same, 2, partner, counts, &info) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "strictly increasing") != nullptr);
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 1ull << 31, 2, dist, ops.data(), usym, 2, partner, counts,
+                                &info) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "below 2^32") != nullptr);
+    std::vector<nmz_edit_op> bad(ops);
+    bad[1].a_pos = 4;
+    CHECK(nmz_move_profile_host(off, sym.data(), 2, pairs, 2, 2, dist, bad.data(), usym, 2, partner, counts, &info) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "a_pos 4 is outside") != nullptr);
+    bad[1] = nmz_edit_op{3, 4, 7};
+    CHECK(nmz_script_moves_host(ab.data(), 4, ba.data(), 4, bad.data(), 2, pr2) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "op kind 7") != nullptr);
+    CHECK(nmz_move_profile(nullptr, off, sym.data(), 2, pairs, 2, 2, dist, ops.data(), usym, 2, partner, counts, &info) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    CHECK(nmz_ed_diff_profile(nullptr, off, sym.data(), 2, pairs, 2, 2, usym, 2, nullptr, counts, &info) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    CHECK(nmz_move_profile_dev(nullptr, off, sym.data(), pairs, 2, 2, dist, ops.data(), usym, 2, partner, counts, &info, 0,
+                               nullptr) == NMZ_EINVAL);
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -459,6 +556,7 @@ int main() {
     delivery_cases();
     match_cases();
     align_cases();
+    moves_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
