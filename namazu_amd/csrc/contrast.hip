@@ -258,7 +258,7 @@ static int contrast_labels(const uint8_t *failed, uint32_t R, uint32_t *n_fail) 
 }
 
 
-// enqueue one contrast on st; scratch: ctx->buf[18] (the run order, the merged list, the per-workgroup lists)
+// enqueue one contrast on st; scratch: SLOT_CONTRAST_RUN (the run order, the merged list, the per-workgroup lists)
 static int contrast_run(nmz_ctx *ctx, hipStream_t st, const uint32_t *d_pos, const uint8_t *d_failed, uint32_t R,
                         uint32_t E, uint32_t k, nmz_pair_counts *d_counts, nmz_order_pair *d_pairs,
                         nmz_contrast_info *d_info) {
@@ -268,13 +268,11 @@ static int contrast_run(nmz_ctx *ctx, hipStream_t st, const uint32_t *d_pos, con
     NMZ_CHECK(k == 0 || d_pairs, "d_pairs is NULL");
     const uint32_t tiles_a = ceil_div(E, CT_COLS), tiles_b = ceil_div(E, CT_ROWS);
     const uint64_t lists = (uint64_t)tiles_a * tiles_b;  // one per workgroup: at most 8,192
-    NMZ_TRY(ctx->buf[18].ensure(Carve::bytes_for(R, 4) + Carve::bytes_for(k + 1, sizeof(nmz_topk_entry)) +
-                                2 * Carve::bytes_for(lists * k + 1, sizeof(nmz_topk_entry))));
-    Carve cv(ctx->buf[18].ptr);
-    uint32_t *d_perm = cv.take<uint32_t>(R);
-    nmz_topk_entry *d_tk = cv.take<nmz_topk_entry>(k + 1);
-    nmz_topk_entry *la = cv.take<nmz_topk_entry>(lists * k + 1);
-    nmz_topk_entry *lb = cv.take<nmz_topk_entry>(lists * k + 1);
+    uint32_t *d_perm;
+    nmz_topk_entry *d_tk, *la, *lb;
+    ScratchLayout lay;
+    lay.add(&d_perm, R).add(&d_tk, k + 1).add(&la, lists * k + 1).add(&lb, lists * k + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_CONTRAST_RUN]));
     hipLaunchKernelGGL(k_contrast_runs, dim3(1), dim3(CT_RUNS_THREADS), 0, st, d_failed, R, d_perm, d_info);
     if (hipGetLastError() != hipSuccess) return fail(NMZ_EHIP, "k_contrast_runs launch failed");
     {
@@ -364,25 +362,24 @@ int nmz_order_contrast(nmz_ctx *ctx, const uint32_t *pos, const uint8_t *failed,
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     hipStream_t st = ctx->stream;
-    const size_t cells = (size_t)n_runs * n_events, sq = (size_t)n_events * n_events;
-    NMZ_TRY(ctx->buf[19].ensure(Carve::bytes_for(cells, 4) + Carve::bytes_for(n_runs, 1) +
-                                Carve::bytes_for(counts ? sq : 1, sizeof(nmz_pair_counts)) +
-                                Carve::bytes_for(k + 1, sizeof(nmz_order_pair)) +
-                                Carve::bytes_for(1, sizeof(nmz_contrast_info))));
-    Carve cv(ctx->buf[19].ptr);
-    uint32_t *d_pos = cv.take<uint32_t>(cells);
-    uint8_t *d_failed = cv.take<uint8_t>(n_runs);
-    nmz_pair_counts *d_counts = cv.take<nmz_pair_counts>(counts ? sq : 1);
-    nmz_order_pair *d_pairs = cv.take<nmz_order_pair>(k + 1);
-    nmz_contrast_info *d_info = cv.take<nmz_contrast_info>(1);
-    NMZ_HIP(hipMemcpyAsync(d_pos, pos, cells * 4, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_failed, failed, n_runs, hipMemcpyHostToDevice, st));
-    NMZ_TRY(contrast_run(ctx, st, d_pos, d_failed, n_runs, n_events, k, counts ? d_counts : nullptr, d_pairs, d_info));
     nmz_contrast_info hinfo{};
-    if (counts) NMZ_HIP(hipMemcpyAsync(counts, d_counts, sq * sizeof(nmz_pair_counts), hipMemcpyDeviceToHost, st));
-    if (k) NMZ_HIP(hipMemcpyAsync(pairs, d_pairs, k * sizeof(nmz_order_pair), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(&hinfo, d_info, sizeof(hinfo), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
+    HostCall call(ctx);
+    const size_t cells = (size_t)n_runs * n_events, sq = (size_t)n_events * n_events;
+    uint32_t *d_pos;
+    uint8_t *d_failed;
+    nmz_pair_counts *d_counts;
+    nmz_order_pair *d_pairs;
+    nmz_contrast_info *d_info;
+    ScratchLayout lay;
+    lay.add(&d_pos, cells).add(&d_failed, n_runs).add(&d_counts, counts ? sq : 1).add(&d_pairs, k + 1).add(&d_info, 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_CONTRAST_HOST]));
+    NMZ_TRY(copy_h2d(d_pos, pos, cells, st));
+    NMZ_TRY(copy_h2d(d_failed, failed, n_runs, st));
+    NMZ_TRY(contrast_run(ctx, st, d_pos, d_failed, n_runs, n_events, k, counts ? d_counts : nullptr, d_pairs, d_info));
+    if (counts) NMZ_TRY(copy_d2h(counts, d_counts, sq, st));
+    NMZ_TRY(copy_d2h(pairs, d_pairs, k, st));
+    NMZ_TRY(copy_d2h(&hinfo, d_info, 1, st));
+    NMZ_TRY(call.done());
     if (info) *info = hinfo;
     return NMZ_OK;
 }
@@ -406,24 +403,23 @@ int nmz_order_contrast_runs(nmz_ctx *ctx, const uint64_t *sym, const int64_t *ar
     NMZ_TRY(g.rc);
     hipStream_t st = ctx->stream;
     nmz_contrast_info hinfo{};
-    MatchCall call(ctx);  // behind hinfo: its destructor drains the stream that copies into it
+    HostCall call(ctx);
     const size_t sq = (size_t)n_events * n_events;
-    NMZ_TRY(ctx->buf[19].ensure(Carve::bytes_for(n_runs, 1) + Carve::bytes_for(counts ? sq : 1, sizeof(nmz_pair_counts)) +
-                                Carve::bytes_for(k + 1, sizeof(nmz_order_pair)) +
-                                Carve::bytes_for(1, sizeof(nmz_contrast_info))));
-    Carve cv(ctx->buf[19].ptr);
-    uint8_t *d_failed = cv.take<uint8_t>(n_runs);
-    nmz_pair_counts *d_counts = cv.take<nmz_pair_counts>(counts ? sq : 1);
-    nmz_order_pair *d_pairs = cv.take<nmz_order_pair>(k + 1);
-    nmz_contrast_info *d_info = cv.take<nmz_contrast_info>(1);
+    uint8_t *d_failed;
+    nmz_pair_counts *d_counts;
+    nmz_order_pair *d_pairs;
+    nmz_contrast_info *d_info;
+    ScratchLayout lay;
+    lay.add(&d_failed, n_runs).add(&d_counts, counts ? sq : 1).add(&d_pairs, k + 1).add(&d_info, 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_CONTRAST_HOST]));
     uint32_t *d_pos = nullptr;
-    NMZ_TRY(call.run(sym, arrival_ns, n_events, run_off, run_sym, n_runs, &d_pos));
-    NMZ_HIP(hipMemcpyAsync(d_failed, failed, n_runs, hipMemcpyHostToDevice, st));
+    NMZ_TRY(match_call(ctx, call, sym, arrival_ns, n_events, run_off, run_sym, n_runs, &d_pos));
+    NMZ_TRY(copy_h2d(d_failed, failed, n_runs, st));
     NMZ_TRY(contrast_run(ctx, st, d_pos, d_failed, n_runs, n_events, k, counts ? d_counts : nullptr, d_pairs, d_info));
-    if (counts) NMZ_HIP(hipMemcpyAsync(counts, d_counts, sq * sizeof(nmz_pair_counts), hipMemcpyDeviceToHost, st));
-    if (k) NMZ_HIP(hipMemcpyAsync(pairs, d_pairs, k * sizeof(nmz_order_pair), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(&hinfo, d_info, sizeof(hinfo), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
+    if (counts) NMZ_TRY(copy_d2h(counts, d_counts, sq, st));
+    NMZ_TRY(copy_d2h(pairs, d_pairs, k, st));
+    NMZ_TRY(copy_d2h(&hinfo, d_info, 1, st));
+    NMZ_TRY(call.done());
     if (info) *info = hinfo;
     return NMZ_OK;
 }

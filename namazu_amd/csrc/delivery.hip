@@ -223,10 +223,11 @@ static int delivery_classes_locked(nmz_ctx *ctx, const nmz_delivery_stats *d_sta
     if (d_n_classes) NMZ_HIP(hipMemsetAsync(d_n_classes, 0, 4, st));
     if (n == 0) return NMZ_OK;
     NMZ_CHECK(d_stats && d_first, "NULL argument");
-    NMZ_TRY(ctx->buf[17].ensure(Carve::bytes_for(2 * (size_t)n, 8) + Carve::bytes_for(n, 8)));
-    Carve cv(ctx->buf[17].ptr);
-    uint64_t *sig = cv.take<uint64_t>(2 * (size_t)n);
-    long long *best = cv.take<long long>(n);
+    uint64_t *sig;
+    long long *best;
+    ScratchLayout lay;
+    lay.add(&sig, 2 * (size_t)n).add(&best, n);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_DELIVERY_CLASSES]));
     const unsigned g = ceil_div(n, 256);
     hipLaunchKernelGGL(k_dlv_unpack, dim3(g), dim3(256), 0, st, d_stats, n, sig, best, d_rep);
     NMZ_HIP(hipGetLastError());
@@ -418,9 +419,14 @@ static int delivery_plan_create_locked(nmz_ctx *ctx, const uint32_t *hint_off, c
             }
     }
     const size_t ns = max_seeds ? max_seeds : 1;
-    int rc = p->mem.ensure(Carve::bytes_for(table.size(), 8) + 3 * Carve::bytes_for(Gp, 8) + Carve::bytes_for(Gp, 4) +
-                           Carve::bytes_for(Gp, 2) + Carve::bytes_for(slot.size(), 2) + Carve::bytes_for(ns, 8) +
-                           Carve::bytes_for(bucket_hist_u32(ns), 4));
+    uint64_t *d_table, *d_pn, *d_sym;
+    int64_t *d_arr;
+    uint32_t *d_orig;
+    uint16_t *d_ss, *d_slot;
+    ScratchLayout lay;
+    lay.add(&d_table, table.size()).add(&d_pn, Gp).add(&d_arr, Gp).add(&d_sym, Gp).add(&d_orig, Gp).add(&d_ss, Gp);
+    lay.add(&d_slot, slot.size()).add(&p->d_h0, ns).add(&p->d_rows, bucket_hist_u32(ns));
+    int rc = lay.bind(p->mem);
     const ulonglong2 *keys = nullptr;
     if (rc == NMZ_OK) rc = sig_rank_keys(ctx, &keys);
     if (rc != NMZ_OK) {
@@ -428,16 +434,6 @@ static int delivery_plan_create_locked(nmz_ctx *ctx, const uint32_t *hint_off, c
         delete p;
         return rc;
     }
-    Carve cv(p->mem.ptr);
-    uint64_t *d_table = cv.take<uint64_t>(table.size());
-    uint64_t *d_pn = cv.take<uint64_t>(Gp);
-    int64_t *d_arr = cv.take<int64_t>(Gp);
-    uint64_t *d_sym = cv.take<uint64_t>(Gp);
-    uint32_t *d_orig = cv.take<uint32_t>(Gp);
-    uint16_t *d_ss = cv.take<uint16_t>(Gp);
-    uint16_t *d_slot = cv.take<uint16_t>(slot.size());
-    p->d_h0 = cv.take<uint64_t>(ns);
-    p->d_rows = cv.take<uint32_t>(bucket_hist_u32(ns));
     p->args = DlvArgs{p->d_h0, d_table, d_pn, d_arr, d_sym, d_orig, d_ss, d_slot, keys,
                       nullptr, 0,      p->m, p->mu, G,      p->net, K};
     hipStream_t st = ctx->stream;
@@ -528,44 +524,33 @@ static int delivery_sweep_host(nmz_ctx *ctx, const uint32_t *seed_off, const uin
     NMZ_CHECK(!classes || n_seeds < (1ULL << 31), "at most 2^31-1 seeds per call with classes");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
+    HostCall call(ctx);
     nmz_replayable_delivery_plan *plan = nullptr;
     NMZ_TRY(delivery_plan_create_locked(ctx, hint_off, hint_bytes, n_events, max_interval_ns, arrival_ns, sym, entity,
                                         n_seeds, &plan));
-    struct PlanGuard {
-        nmz_replayable_delivery_plan *p;
-        ~PlanGuard() { delivery_plan_destroy_locked(p); }
-    } pg{plan};
+    call.own_plan<delivery_plan_destroy_locked>(plan);
     hipStream_t st = ctx->stream;
-    const uint64_t sbytes = (!decimal && n_seeds) ? seed_off[n_seeds] : 0;
-    NMZ_CHECK(sbytes == 0 || seed_bytes, "seed_bytes is NULL");
-    NMZ_TRY(ctx->buf[16].ensure(Carve::bytes_for(n_seeds + 1, 4) + Carve::bytes_for(sbytes + 1, 1) +
-                                Carve::bytes_for(n_seeds + 1, sizeof(nmz_delivery_stats)) +
-                                2 * Carve::bytes_for(n_seeds + 1, 4) + Carve::bytes_for(1, 4)));
-    Carve cv(ctx->buf[16].ptr);
-    uint32_t *d_soff = cv.take<uint32_t>(n_seeds + 1);
-    uint8_t *d_sb = cv.take<uint8_t>(sbytes + 1);
-    nmz_delivery_stats *d_stats = cv.take<nmz_delivery_stats>(n_seeds + 1);
-    uint32_t *d_first = cv.take<uint32_t>(n_seeds + 1);
-    uint32_t *d_rep = cv.take<uint32_t>(n_seeds + 1);
-    uint32_t *d_nc = cv.take<uint32_t>(1);
-    if (!decimal && n_seeds) {
-        NMZ_HIP(hipMemcpyAsync(d_soff, seed_off, (n_seeds + 1) * 4, hipMemcpyHostToDevice, st));
-        if (sbytes) NMZ_HIP(hipMemcpyAsync(d_sb, seed_bytes, sbytes, hipMemcpyHostToDevice, st));
-    }
+    uint64_t sbytes;
+    NMZ_TRY(seed_csr_bytes(seed_off, seed_bytes, n_seeds, decimal, &sbytes));
+    uint32_t *d_soff, *d_first, *d_rep, *d_nc;
+    uint8_t *d_sb;
+    nmz_delivery_stats *d_stats;
+    ScratchLayout lay;
+    lay.add(&d_soff, n_seeds + 1).add(&d_sb, sbytes + 1).add(&d_stats, n_seeds + 1);
+    lay.add(&d_first, n_seeds + 1).add(&d_rep, n_seeds + 1).add(&d_nc, 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_TARGET_DELIVERY_HOST]));
+    NMZ_TRY(upload_seeds(d_soff, d_sb, seed_off, seed_bytes, n_seeds, decimal, st));
     NMZ_TRY(delivery_run(plan, st, decimal ? nullptr : d_soff, d_sb, seed_lo, n_seeds, d_stats));
     if (classes) {
         KernelTimer kt(ctx, st, "delivery_classes");
         NMZ_TRY(delivery_classes_locked(ctx, d_stats, (uint32_t)n_seeds, d_first, class_rep ? d_rep : nullptr,
                                         n_classes ? d_nc : nullptr, st));
     }
-    if (n_seeds) {
-        if (stats) NMZ_HIP(hipMemcpyAsync(stats, d_stats, n_seeds * sizeof(nmz_delivery_stats), hipMemcpyDeviceToHost, st));
-        if (first_equal) NMZ_HIP(hipMemcpyAsync(first_equal, d_first, n_seeds * 4, hipMemcpyDeviceToHost, st));
-        if (class_rep) NMZ_HIP(hipMemcpyAsync(class_rep, d_rep, n_seeds * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (n_classes) NMZ_HIP(hipMemcpyAsync(n_classes, d_nc, 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (stats) NMZ_TRY(copy_d2h(stats, d_stats, n_seeds, st));
+    if (first_equal) NMZ_TRY(copy_d2h(first_equal, d_first, n_seeds, st));
+    if (class_rep) NMZ_TRY(copy_d2h(class_rep, d_rep, n_seeds, st));
+    if (n_classes) NMZ_TRY(copy_d2h(n_classes, d_nc, 1, st));
+    return call.done();
 }
 
 }  // namespace nmz

@@ -310,14 +310,13 @@ void knn_fill_launch(uint64_t *knn, uint32_t n_lists, uint32_t k, uint32_t n_can
                        self_exclude);
 }
 
-int knn_final_to_host(const uint64_t *knn, uint64_t n, uint32_t *d_id, uint32_t *d_ds, uint32_t *knn_id,
-                      uint32_t *knn_dist, hipStream_t st) {
-    hipLaunchKernelGGL(k_knn_final, dim3(ceil_div(n, 256)), dim3(256), 0, st, knn, n, d_id, d_ds);
+int knn_final_to_host(HostCall &call, const uint64_t *knn, uint64_t n, uint32_t *d_id, uint32_t *d_ds,
+                      uint32_t *knn_id, uint32_t *knn_dist) {
+    hipLaunchKernelGGL(k_knn_final, dim3(ceil_div(n, 256)), dim3(256), 0, call.st, knn, n, d_id, d_ds);
     NMZ_HIP(hipGetLastError());
-    if (knn_id) NMZ_HIP(hipMemcpyAsync(knn_id, d_id, n * 4, hipMemcpyDeviceToHost, st));
-    if (knn_dist) NMZ_HIP(hipMemcpyAsync(knn_dist, d_ds, n * 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (knn_id) NMZ_TRY(copy_d2h(knn_id, d_id, n, call.st));
+    if (knn_dist) NMZ_TRY(copy_d2h(knn_dist, d_ds, n, call.st));
+    return call.done();
 }
 
 static int ed_knn_run(nmz_ed_plan *p, hipStream_t st, uint32_t k, uint64_t *d_knn, uint32_t shard = 0,
@@ -425,13 +424,10 @@ static int ed_knn_run(nmz_ed_plan *p, hipStream_t st, uint32_t k, uint64_t *d_kn
     const uint64_t total_pairs = (uint64_t)N * (N - 1) / 2;
     const uint64_t chunk = std::min<uint64_t>(total_pairs, 1ULL << 22);
     const unsigned gthreads = 256 * 1024;
-    DevBuf &scr = p->ctx->buf[3];
-    NMZ_TRY(scr.ensure(Carve::bytes_for(chunk * 2 + 1, 4) + Carve::bytes_for(chunk + 1, 4) +
-                       Carve::bytes_for((uint64_t)(2 * p->band + 1) * gthreads, 4)));
-    Carve cv(scr.ptr);
-    uint32_t *d_pairs = cv.take<uint32_t>(chunk * 2 + 1);
-    uint32_t *d_dist = cv.take<uint32_t>(chunk + 1);
-    uint32_t *d_row = cv.take<uint32_t>((uint64_t)(2 * p->band + 1) * gthreads);
+    uint32_t *d_pairs, *d_dist, *d_row;
+    ScratchLayout lay;
+    lay.add(&d_pairs, chunk * 2 + 1).add(&d_dist, chunk + 1).add(&d_row, (uint64_t)(2 * p->band + 1) * gthreads);
+    NMZ_TRY(lay.bind(p->ctx->buf[SLOT_ED_KNN]));
     for (uint64_t s = (uint64_t)shard * chunk; s < total_pairs; s += (uint64_t)n_shards * chunk) {
         const uint64_t c = std::min(chunk, total_pairs - s);
         hipLaunchKernelGGL(k_pairs_upper, dim3(ceil_div(c, 256)), dim3(256), 0, st, N, s, c, d_pairs);
@@ -586,15 +582,15 @@ int nmz_ed_allpairs_knn(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, 
     nmz_ed_plan *plan = nullptr;
     NMZ_TRY(ed_plan_build(ctx, off, sym, n_traces, band, &plan));
     EdPlanPtr owner(plan);
-    hipStream_t st = ctx->stream;
+    HostCall call(ctx);  // behind owner: the plan goes after the drain
     const uint64_t nk = (uint64_t)n_traces * k;
-    NMZ_TRY(ctx->buf[2].ensure(Carve::bytes_for(nk, 8) + Carve::bytes_for(nk, 4) * 2));
-    Carve cv(ctx->buf[2].ptr);
-    uint64_t *d_knn = cv.take<uint64_t>(nk);
-    uint32_t *d_id = cv.take<uint32_t>(nk);
-    uint32_t *d_ds = cv.take<uint32_t>(nk);
-    NMZ_TRY(ed_knn_run(plan, st, k, d_knn));
-    return knn_final_to_host(d_knn, nk, d_id, d_ds, knn_id, knn_dist, st);
+    uint64_t *d_knn;
+    uint32_t *d_id, *d_ds;
+    ScratchLayout lay;
+    lay.add(&d_knn, nk).add(&d_id, nk).add(&d_ds, nk);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_ED_KNN_HOST]));
+    NMZ_TRY(ed_knn_run(plan, call.st, k, d_knn));
+    return knn_final_to_host(call, d_knn, nk, d_id, d_ds, knn_id, knn_dist);
 }
 
 int nmz_ed_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
@@ -607,26 +603,23 @@ int nmz_ed_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_
     NMZ_CHECK(pairs && dist && off, "NULL argument");
     for (uint64_t t = 0; t < 2 * n_pairs; ++t) NMZ_CHECK(pairs[t] < n_traces, "pair index out of range");
     hipStream_t st = ctx->stream;
-    const uint64_t total = n_traces ? off[n_traces] : 0;
+    HostCall call(ctx);
+    // n_pairs > 0 and every pair index is below n_traces, so there is a trace and off[n_traces] is the total
+    const uint64_t total = off[n_traces];
     const unsigned gthreads = (unsigned)std::min<uint64_t>(256 * 1024, (n_pairs + 255) / 256 * 256);
-    NMZ_TRY(ctx->buf[4].ensure(Carve::bytes_for(n_traces + 1, 8) + Carve::bytes_for(total + 1, 8) +
-                               Carve::bytes_for(2 * n_pairs, 4) + Carve::bytes_for(n_pairs, 4) +
-                               Carve::bytes_for((uint64_t)(2 * band + 1) * gthreads, 4)));
-    Carve cv(ctx->buf[4].ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n_traces + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    uint32_t *d_pairs = cv.take<uint32_t>(2 * n_pairs);
-    uint32_t *d_dist = cv.take<uint32_t>(n_pairs);
-    uint32_t *d_row = cv.take<uint32_t>((uint64_t)(2 * band + 1) * gthreads);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, (n_traces + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, sym, total * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_pairs, pairs, 2 * n_pairs * 4, hipMemcpyHostToDevice, st));
+    uint64_t *d_off, *d_sym;
+    uint32_t *d_pairs, *d_dist, *d_row;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_pairs, 2 * n_pairs).add(&d_dist, n_pairs);
+    lay.add(&d_row, (uint64_t)(2 * band + 1) * gthreads);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_ED_PAIRS_HOST]));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    NMZ_TRY(copy_h2d(d_pairs, pairs, 2 * n_pairs, st));
     hipLaunchKernelGGL(k_ed_generic, dim3(gthreads / 256), dim3(256), 0, st, d_off, d_sym, d_pairs, n_pairs, band, d_row,
                        d_dist);
     NMZ_HIP(hipGetLastError());
-    NMZ_HIP(hipMemcpyAsync(dist, d_dist, n_pairs * 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    NMZ_TRY(copy_d2h(dist, d_dist, n_pairs, st));
+    return call.done();
 }
 
 }  // extern "C"

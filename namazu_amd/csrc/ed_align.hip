@@ -354,12 +354,6 @@ int align_enqueue(nmz_ed_align_plan *p, hipStream_t st, const uint64_t *d_off, c
     return rc;
 }
 
-AlignCall::~AlignCall() {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (plan) align_plan_destroy_locked(plan);
-    work.release();
-}
-
 }  // namespace nmz
 
 using namespace nmz;
@@ -474,28 +468,26 @@ int nmz_ed_align_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, u
     NMZ_CHECK(ctx != nullptr, "ctx is NULL");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
-    AlignCall call(ctx);
-    NMZ_TRY(align_plan_create_locked(ctx, band, max_len, slot_words, &call.plan));
+    HostCall call(ctx);
+    nmz_ed_align_plan *plan = nullptr;
+    NMZ_TRY(align_plan_create_locked(ctx, band, max_len, slot_words, &plan));
+    call.own_plan<align_plan_destroy_locked>(plan);
     hipStream_t st = ctx->stream;
     const uint64_t total = off[n_traces];
     const size_t n_ops = (size_t)n_pairs * band;
-    NMZ_TRY(call.work.ensure(Carve::bytes_for(n_traces + 1, 8) + Carve::bytes_for(total + 1, 8) +
-                             Carve::bytes_for(2 * n_pairs, 4) + Carve::bytes_for(n_pairs, 4) +
-                             Carve::bytes_for(n_ops + 1, sizeof(nmz_edit_op))));
-    Carve cv(call.work.ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n_traces + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    uint32_t *d_pairs = cv.take<uint32_t>(2 * n_pairs);
-    uint32_t *d_dist = cv.take<uint32_t>(n_pairs);
-    nmz_edit_op *d_ops = cv.take<nmz_edit_op>(n_ops + 1);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, ((size_t)n_traces + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, sym, total * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_pairs, pairs, 2 * n_pairs * 4, hipMemcpyHostToDevice, st));
-    NMZ_TRY(align_enqueue(call.plan, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops));
-    NMZ_HIP(hipMemcpyAsync(dist, d_dist, n_pairs * 4, hipMemcpyDeviceToHost, st));
-    if (n_ops) NMZ_HIP(hipMemcpyAsync(ops, d_ops, n_ops * sizeof(nmz_edit_op), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    uint64_t *d_off, *d_sym;
+    uint32_t *d_pairs, *d_dist;
+    nmz_edit_op *d_ops;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_pairs, 2 * n_pairs).add(&d_dist, n_pairs);
+    lay.add(&d_ops, n_ops + 1);
+    NMZ_TRY(lay.bind(call.work));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    NMZ_TRY(copy_h2d(d_pairs, pairs, 2 * n_pairs, st));
+    NMZ_TRY(align_enqueue(plan, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops));
+    NMZ_TRY(copy_d2h(dist, d_dist, n_pairs, st));
+    NMZ_TRY(copy_d2h(ops, d_ops, n_ops, st));
+    return call.done();
 }
 
 }  // extern "C"

@@ -184,21 +184,14 @@ static BvStreams bv_plan_streams(nmz_ed_plan *p, const uint64_t *off) {
 // and the counters' first clear. d_bsym is left for the builder to fill.
 static int bv_plan_storage(nmz_ed_plan *p, const BvStreams &s, const uint64_t *off, hipStream_t st) {
     const uint32_t N = p->n, G = p->G;
-    NMZ_TRY(p->mem.ensure(Carve::bytes_for(s.bs_n, 2) + Carve::bytes_for(N + 1, 8) * 2 + Carve::bytes_for(G + 1, 8) +
-                          Carve::bytes_for(N + 1, 4) + Carve::bytes_for(ED_CNT_WORDS, 8) +
-                          Carve::bytes_for((uint64_t)N * ED_QG_DW, 4)));
-    Carve cv(p->mem.ptr);
-    p->d_counters = cv.take<uint64_t>(ED_CNT_WORDS);
-    p->d_prof = cv.take<uint32_t>((uint64_t)N * ED_QG_DW);
-    p->d_bsym = cv.take<uint16_t>(s.bs_n);
-    p->d_soff = cv.take<uint64_t>(N + 1);
-    p->d_qoff = cv.take<uint64_t>(N + 1);
-    p->d_chunk_start = cv.take<uint64_t>(G + 1);
-    p->d_len = cv.take<uint32_t>(N + 1);
-    NMZ_HIP(hipMemcpyAsync(p->d_soff, s.soff.data(), (N + 1) * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_qoff, off, (N + 1) * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_chunk_start, s.chunk_start.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_len, s.len.data(), (N + 1) * 4, hipMemcpyHostToDevice, st));
+    ScratchLayout lay;
+    lay.add(&p->d_counters, ED_CNT_WORDS).add(&p->d_prof, (uint64_t)N * ED_QG_DW).add(&p->d_bsym, s.bs_n);
+    lay.add(&p->d_soff, N + 1).add(&p->d_qoff, N + 1).add(&p->d_chunk_start, G + 1).add(&p->d_len, N + 1);
+    NMZ_TRY(lay.bind(p->mem));
+    NMZ_TRY(copy_h2d(p->d_soff, s.soff.data(), (size_t)N + 1, st));
+    NMZ_TRY(copy_h2d(p->d_qoff, off, (size_t)N + 1, st));
+    NMZ_TRY(copy_h2d(p->d_chunk_start, s.chunk_start.data(), (size_t)G + 1, st));
+    NMZ_TRY(copy_h2d(p->d_len, s.len.data(), (size_t)N + 1, st));
     NMZ_HIP(hipMemsetAsync(p->d_counters, 0, ED_CNT_WORDS * 8, st));
     return NMZ_OK;
 }
@@ -215,18 +208,15 @@ static int device_symbols(DevBuf &tmp, const uint64_t *off, const uint64_t *sym,
                           uint32_t n_off, hipStream_t st, DeviceSymbols &D) {
     const uint64_t total = off[N];
     NMZ_CHECK(total == 0 || sym || d_sym_in, "sym is NULL");
-    NMZ_TRY(tmp.ensure(Carve::bytes_for(d_sym_in ? 0 : total, 8) + Carve::bytes_for(MAX_FAST_SYMBOLS + 1, 8) +
-                       Carve::bytes_for(N + 1, 8) * n_off));
-    Carve tv(tmp.ptr);
-    D.d_sym = d_sym_in;
-    if (!d_sym_in) {
-        uint64_t *d_up = tv.take<uint64_t>(total);
-        NMZ_HIP(hipMemcpyAsync(d_up, sym, total * 8, hipMemcpyHostToDevice, st));
-        D.d_sym = d_up;
-    }
-    D.d_uniq = tv.take<uint64_t>(MAX_FAST_SYMBOLS + 1);
-    for (uint32_t i = 0; i < n_off; ++i) D.d_off[i] = tv.take<uint64_t>(N + 1);
-    NMZ_HIP(hipMemcpyAsync(D.d_off[0], off, (N + 1) * 8, hipMemcpyHostToDevice, st));
+    uint64_t *d_up = nullptr;
+    ScratchLayout lay;
+    if (!d_sym_in) lay.add(&d_up, total);
+    lay.add(&D.d_uniq, MAX_FAST_SYMBOLS + 1);
+    for (uint32_t i = 0; i < n_off; ++i) lay.add(&D.d_off[i], N + 1);
+    NMZ_TRY(lay.bind(tmp));
+    NMZ_TRY(copy_h2d(d_up, sym, d_sym_in ? 0 : total, st));
+    D.d_sym = d_sym_in ? d_sym_in : d_up;
+    NMZ_TRY(copy_h2d(D.d_off[0], off, (size_t)N + 1, st));
     return device_unique_u64(D.d_sym, total, D.d_uniq, MAX_FAST_SYMBOLS, &D.n_uniq, st);
 }
 
@@ -263,12 +253,14 @@ static int ed_plan_build_bv_device(nmz_ed_plan *p, const uint64_t *off, const ui
     if (p->cmp) {  // the traces' distinct counts size the per-workgroup rows
         DevBuf dbuf;
         ScopedRelease rel{dbuf};
-        NMZ_TRY(dbuf.ensure(Carve::bytes_for(N + 1, 4)));
+        uint32_t *d_distinct;
+        ScratchLayout dlay;
+        NMZ_TRY(dlay.add(&d_distinct, N + 1).bind(dbuf));
         hipLaunchKernelGGL(k_trace_distinct, dim3(N), dim3(256), ((n_sym + 32) / 32) * 4, st, p->d_bsym, p->d_soff,
-                           p->d_len, n_sym + 1, dbuf.as<uint32_t>());
+                           p->d_len, n_sym + 1, d_distinct);
         NMZ_HIP(hipGetLastError());
         std::vector<uint32_t> d(N);
-        NMZ_HIP(hipMemcpyAsync(d.data(), dbuf.ptr, (uint64_t)N * 4, hipMemcpyDeviceToHost, st));
+        NMZ_TRY(copy_d2h(d.data(), d_distinct, N, st));
         NMZ_HIP(hipStreamSynchronize(st));
         if (!bv_plan_compact(p, d)) return 1;  // the host build's other kernels
     }
@@ -336,17 +328,12 @@ static std::vector<uint64_t> wide_plan_roff(const uint64_t *off, uint32_t N) {
 static int wide_plan_storage(nmz_ed_plan *p, const uint64_t *off, const std::vector<uint64_t> &roff, hipStream_t st) {
     const uint32_t N = p->n;
     const uint64_t total = p->total, nrow = roff[N] + 1;
-    NMZ_TRY(p->mem.ensure(Carve::bytes_for(total + 64, 2) + Carve::bytes_for(N + 1, 8) +
-                          Carve::bytes_for((uint64_t)N * p->n_sym * p->ndw, 4) + Carve::bytes_for(nrow, 4) +
-                          Carve::bytes_for(N + 1, 8)));
-    Carve cv(p->mem.ptr);
-    p->d_qsym = cv.take<uint16_t>(total + 64);
-    p->d_qoff = cv.take<uint64_t>(N + 1);
-    p->d_peq = cv.take<uint32_t>((uint64_t)N * p->n_sym * p->ndw);
-    p->d_rowb = cv.take<uint32_t>(nrow);
-    p->d_rowb_off = cv.take<uint64_t>(N + 1);
-    NMZ_HIP(hipMemcpyAsync(p->d_qoff, off, (N + 1) * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_rowb_off, roff.data(), (N + 1) * 8, hipMemcpyHostToDevice, st));
+    ScratchLayout lay;
+    lay.add(&p->d_qsym, total + 64).add(&p->d_qoff, N + 1).add(&p->d_peq, (uint64_t)N * p->n_sym * p->ndw);
+    lay.add(&p->d_rowb, nrow).add(&p->d_rowb_off, N + 1);
+    NMZ_TRY(lay.bind(p->mem));
+    NMZ_TRY(copy_h2d(p->d_qoff, off, (size_t)N + 1, st));
+    NMZ_TRY(copy_h2d(p->d_rowb_off, roff.data(), (size_t)N + 1, st));
     NMZ_HIP(hipMemsetAsync(p->d_qsym, 0, (total + 64) * 2, st));
     return NMZ_OK;
 }
@@ -365,7 +352,7 @@ static int ed_plan_build_wide_device(nmz_ed_plan *p, const uint64_t *off, const 
     if (D.n_uniq >= MAX_FAST_SYMBOLS || !wide_plan_shape(p, (uint32_t)D.n_uniq)) return 1;
     const std::vector<uint64_t> roff = wide_plan_roff(off, N);
     NMZ_TRY(wide_plan_storage(p, off, roff, st));
-    NMZ_HIP(hipMemcpyAsync(D.d_off[1], roff.data(), (N + 1) * 8, hipMemcpyHostToDevice, st));
+    NMZ_TRY(copy_h2d(D.d_off[1], roff.data(), (size_t)N + 1, st));
     NMZ_HIP(hipMemsetAsync(p->d_rowb, 0, (roff[N] + 1) * 4, st));
     if (N) {
         hipLaunchKernelGGL(k_ed_wide_remap, dim3(N), dim3(256), 0, st, D.d_off[0], D.d_sym, D.d_uniq,
@@ -389,8 +376,8 @@ static int ed_plan_build_wide_host(nmz_ed_plan *p, const uint64_t *off, const st
     for (uint32_t i = 0; i < N; ++i)
         for (uint64_t t = off[i]; t < off[i + 1]; ++t) rowb[roff[i] + (t - off[i])] = ids[t] * p->ndw * 4;
     NMZ_TRY(wide_plan_storage(p, off, roff, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_rowb, rowb.data(), rowb.size() * 4, hipMemcpyHostToDevice, st));
-    if (p->total) NMZ_HIP(hipMemcpyAsync(p->d_qsym, ids.data(), p->total * 2, hipMemcpyHostToDevice, st));
+    NMZ_TRY(copy_h2d(p->d_rowb, rowb.data(), rowb.size(), st));
+    NMZ_TRY(copy_h2d(p->d_qsym, ids.data(), p->total, st));
     NMZ_TRY(ed_wide_build_peq(p->d_qsym, p->d_qoff, N, p->n_sym, p->ndw, p->ww, p->d_peq, st));
     NMZ_HIP(hipStreamSynchronize(st));
     p->dict = std::move(dict);
@@ -418,22 +405,16 @@ static int ed_plan_build_tile(nmz_ed_plan *p, const uint64_t *off, const std::ve
         const uint64_t base = coff[i / 64] + (i % 64);
         for (uint32_t t = 0; t < len[i]; ++t) cs[base + (uint64_t)t * 64] = ids[off[i] + t];
     }
-    NMZ_TRY(p->mem.ensure(Carve::bytes_for(total + 1, 2) + Carve::bytes_for(cs.size(), 2) +
-                          Carve::bytes_for(N + 1, 8) + Carve::bytes_for(G + 1, 8) + Carve::bytes_for(G + 1, 4) +
-                          Carve::bytes_for(N + 1, 4)));
-    Carve cv(p->mem.ptr);
-    p->d_qsym = cv.take<uint16_t>(total + 1);
-    p->d_csym = cv.take<uint16_t>(cs.size());
-    p->d_qoff = cv.take<uint64_t>(N + 1);
-    p->d_coff = cv.take<uint64_t>(G + 1);
-    p->d_gmax = cv.take<uint32_t>(G + 1);
-    p->d_len = cv.take<uint32_t>(N + 1);
-    if (total) NMZ_HIP(hipMemcpyAsync(p->d_qsym, ids.data(), total * 2, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_csym, cs.data(), cs.size() * 2, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_qoff, off, (N + 1) * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_coff, coff.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_gmax, gmax.data(), (G + 1) * 4, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(p->d_len, len.data(), (N + 1) * 4, hipMemcpyHostToDevice, st));
+    ScratchLayout lay;
+    lay.add(&p->d_qsym, total + 1).add(&p->d_csym, cs.size()).add(&p->d_qoff, N + 1).add(&p->d_coff, G + 1);
+    lay.add(&p->d_gmax, G + 1).add(&p->d_len, N + 1);
+    NMZ_TRY(lay.bind(p->mem));
+    NMZ_TRY(copy_h2d(p->d_qsym, ids.data(), total, st));
+    NMZ_TRY(copy_h2d(p->d_csym, cs.data(), cs.size(), st));
+    NMZ_TRY(copy_h2d(p->d_qoff, off, (size_t)N + 1, st));
+    NMZ_TRY(copy_h2d(p->d_coff, coff.data(), (size_t)G + 1, st));
+    NMZ_TRY(copy_h2d(p->d_gmax, gmax.data(), (size_t)G + 1, st));
+    NMZ_TRY(copy_h2d(p->d_len, len.data(), (size_t)N + 1, st));
     NMZ_HIP(hipStreamSynchronize(st));
     p->dict = std::move(dict);
     p->tile = p->fast = true;
@@ -444,12 +425,10 @@ static int ed_plan_build_tile(nmz_ed_plan *p, const uint64_t *off, const std::ve
 static int ed_plan_build_generic(nmz_ed_plan *p, const uint64_t *off, const uint64_t *sym) {
     hipStream_t st = p->ctx->stream;
     const uint32_t N = p->n;
-    NMZ_TRY(p->mem.ensure(Carve::bytes_for(N + 1, 8) + Carve::bytes_for(p->total + 1, 8)));
-    Carve cv(p->mem.ptr);
-    p->d_off64 = cv.take<uint64_t>(N + 1);
-    p->d_sym64 = cv.take<uint64_t>(p->total + 1);
-    NMZ_HIP(hipMemcpyAsync(p->d_off64, off, (N + 1) * 8, hipMemcpyHostToDevice, st));
-    if (p->total) NMZ_HIP(hipMemcpyAsync(p->d_sym64, sym, p->total * 8, hipMemcpyHostToDevice, st));
+    ScratchLayout lay;
+    NMZ_TRY(lay.add(&p->d_off64, N + 1).add(&p->d_sym64, p->total + 1).bind(p->mem));
+    NMZ_TRY(copy_h2d(p->d_off64, off, (size_t)N + 1, st));
+    NMZ_TRY(copy_h2d(p->d_sym64, sym, p->total, st));
     NMZ_HIP(hipStreamSynchronize(st));
     return NMZ_OK;
 }

@@ -410,39 +410,32 @@ int nmz_move_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uin
     NMZ_CHECK(ctx != nullptr, "ctx is NULL");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
-    AlignCall call(ctx);  // no plan: the buffers, and the drain before they go back
+    HostCall call(ctx);  // owns no plan: call.work holds the buffers, drained before they go back to the pool
     hipStream_t st = ctx->stream;
     const uint64_t total = off[n_traces];
     const size_t n_slots = (size_t)n_pairs * band;
-    NMZ_TRY(call.work.ensure(Carve::bytes_for(n_traces + 1, 8) + Carve::bytes_for(total + 1, 8) +
-                             Carve::bytes_for(2 * n_pairs, 4) + Carve::bytes_for(n_pairs, 4) +
-                             Carve::bytes_for(n_slots + 1, sizeof(nmz_edit_op)) + Carve::bytes_for(n_usym + 1, 8) +
-                             Carve::bytes_for(n_slots + 1, 4) + Carve::bytes_for(n_usym + 1, sizeof(nmz_move_counts)) +
-                             Carve::bytes_for(1, sizeof(nmz_move_info))));
-    Carve cv(call.work.ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n_traces + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    uint32_t *d_pairs = cv.take<uint32_t>(2 * n_pairs);
-    uint32_t *d_dist = cv.take<uint32_t>(n_pairs);
-    nmz_edit_op *d_ops = cv.take<nmz_edit_op>(n_slots + 1);
-    uint64_t *d_usym = cv.take<uint64_t>(n_usym + 1);
-    uint32_t *d_partner = cv.take<uint32_t>(n_slots + 1);
-    nmz_move_counts *d_counts = cv.take<nmz_move_counts>(n_usym + 1);
-    nmz_move_info *d_info = cv.take<nmz_move_info>(1);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, ((size_t)n_traces + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, sym, total * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_pairs, pairs, 2 * n_pairs * 4, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_dist, dist, n_pairs * 4, hipMemcpyHostToDevice, st));
-    if (n_slots) NMZ_HIP(hipMemcpyAsync(d_ops, ops, n_slots * sizeof(nmz_edit_op), hipMemcpyHostToDevice, st));
-    if (n_usym) NMZ_HIP(hipMemcpyAsync(d_usym, usym, n_usym * 8, hipMemcpyHostToDevice, st));
+    uint64_t *d_off, *d_sym, *d_usym;
+    uint32_t *d_pairs, *d_dist, *d_partner;
+    nmz_edit_op *d_ops;
+    nmz_move_counts *d_counts;
+    nmz_move_info *d_info;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_pairs, 2 * n_pairs).add(&d_dist, n_pairs);
+    lay.add(&d_ops, n_slots + 1).add(&d_usym, n_usym + 1).add(&d_partner, n_slots + 1).add(&d_counts, n_usym + 1);
+    lay.add(&d_info, 1);
+    NMZ_TRY(lay.bind(call.work));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    NMZ_TRY(copy_h2d(d_pairs, pairs, 2 * n_pairs, st));
+    NMZ_TRY(copy_h2d(d_dist, dist, n_pairs, st));
+    NMZ_TRY(copy_h2d(d_ops, ops, n_slots, st));
+    NMZ_TRY(copy_h2d(d_usym, usym, n_usym, st));
     const MvArgs a{d_off, d_sym, d_pairs, n_pairs, band, d_dist, d_ops, d_usym, n_usym, partner ? d_partner : nullptr,
                    d_counts, d_info};
     NMZ_TRY(moves_enqueue(ctx, st, a, 0));
-    if (partner && n_slots) NMZ_HIP(hipMemcpyAsync(partner, d_partner, n_slots * 4, hipMemcpyDeviceToHost, st));
-    if (n_usym) NMZ_HIP(hipMemcpyAsync(counts, d_counts, n_usym * sizeof(nmz_move_counts), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(info, d_info, sizeof(nmz_move_info), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (partner) NMZ_TRY(copy_d2h(partner, d_partner, n_slots, st));
+    NMZ_TRY(copy_d2h(counts, d_counts, n_usym, st));
+    NMZ_TRY(copy_d2h(info, d_info, 1, st));
+    return call.done();
 }
 
 int nmz_ed_diff_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
@@ -460,37 +453,32 @@ int nmz_ed_diff_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, 
     NMZ_CHECK(ctx != nullptr, "ctx is NULL");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
-    AlignCall call(ctx);
-    NMZ_TRY(align_plan_create_locked(ctx, band, max_len, slot_words, &call.plan));
+    HostCall call(ctx);
+    nmz_ed_align_plan *plan = nullptr;
+    NMZ_TRY(align_plan_create_locked(ctx, band, max_len, slot_words, &plan));
+    call.own_plan<align_plan_destroy_locked>(plan);
     hipStream_t st = ctx->stream;
     const uint64_t total = off[n_traces];
     const size_t n_slots = (size_t)n_pairs * band;
-    NMZ_TRY(call.work.ensure(Carve::bytes_for(n_traces + 1, 8) + Carve::bytes_for(total + 1, 8) +
-                             Carve::bytes_for(2 * n_pairs, 4) + Carve::bytes_for(n_pairs, 4) +
-                             Carve::bytes_for(n_slots + 1, sizeof(nmz_edit_op)) + Carve::bytes_for(n_usym + 1, 8) +
-                             Carve::bytes_for(n_usym + 1, sizeof(nmz_move_counts)) +
-                             Carve::bytes_for(1, sizeof(nmz_move_info))));
-    Carve cv(call.work.ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n_traces + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    uint32_t *d_pairs = cv.take<uint32_t>(2 * n_pairs);
-    uint32_t *d_dist = cv.take<uint32_t>(n_pairs);
-    nmz_edit_op *d_ops = cv.take<nmz_edit_op>(n_slots + 1);
-    uint64_t *d_usym = cv.take<uint64_t>(n_usym + 1);
-    nmz_move_counts *d_counts = cv.take<nmz_move_counts>(n_usym + 1);
-    nmz_move_info *d_info = cv.take<nmz_move_info>(1);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, ((size_t)n_traces + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, sym, total * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_pairs, pairs, 2 * n_pairs * 4, hipMemcpyHostToDevice, st));
-    if (n_usym) NMZ_HIP(hipMemcpyAsync(d_usym, usym, n_usym * 8, hipMemcpyHostToDevice, st));
-    NMZ_TRY(align_enqueue(call.plan, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops));
+    uint64_t *d_off, *d_sym, *d_usym;
+    uint32_t *d_pairs, *d_dist;
+    nmz_edit_op *d_ops;
+    nmz_move_counts *d_counts;
+    nmz_move_info *d_info;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_pairs, 2 * n_pairs).add(&d_dist, n_pairs);
+    lay.add(&d_ops, n_slots + 1).add(&d_usym, n_usym + 1).add(&d_counts, n_usym + 1).add(&d_info, 1);
+    NMZ_TRY(lay.bind(call.work));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    NMZ_TRY(copy_h2d(d_pairs, pairs, 2 * n_pairs, st));
+    NMZ_TRY(copy_h2d(d_usym, usym, n_usym, st));
+    NMZ_TRY(align_enqueue(plan, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops));
     const MvArgs a{d_off, d_sym, d_pairs, n_pairs, band, d_dist, d_ops, d_usym, n_usym, nullptr, d_counts, d_info};
     NMZ_TRY(moves_enqueue(ctx, st, a, 0));
-    if (dist) NMZ_HIP(hipMemcpyAsync(dist, d_dist, n_pairs * 4, hipMemcpyDeviceToHost, st));
-    if (n_usym) NMZ_HIP(hipMemcpyAsync(counts, d_counts, n_usym * sizeof(nmz_move_counts), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(info, d_info, sizeof(nmz_move_info), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (dist) NMZ_TRY(copy_d2h(dist, d_dist, n_pairs, st));
+    NMZ_TRY(copy_d2h(counts, d_counts, n_usym, st));
+    NMZ_TRY(copy_d2h(info, d_info, 1, st));
+    return call.done();
 }
 
 }  // extern "C"

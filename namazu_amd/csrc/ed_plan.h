@@ -255,8 +255,8 @@ void knn_init_launch(uint64_t *knn, uint64_t n, hipStream_t st);
 void knn_fill_launch(uint64_t *knn, uint32_t n_lists, uint32_t k, uint32_t n_cand, uint32_t fill_d, int self_exclude,
                      hipStream_t st);
 // a search's end: the lists' ids and distances (k_knn_final into d_id, d_ds) copied to the host; synchronises st
-int knn_final_to_host(const uint64_t *knn, uint64_t n, uint32_t *d_id, uint32_t *d_ds, uint32_t *knn_id,
-                      uint32_t *knn_dist, hipStream_t st);
+int knn_final_to_host(HostCall &call, const uint64_t *knn, uint64_t n, uint32_t *d_id, uint32_t *d_ds,
+                      uint32_t *knn_id, uint32_t *knn_dist);
 
 // the EdWideArgs fields a wide plan fixes: its store, its tables, one shard; the caller adds the lists and the waves
 inline EdWideArgs ed_wide_plan_args(const nmz_ed_plan *p, uint32_t k) {

@@ -42,15 +42,13 @@ static int ed_query_generic_launch(nmz_ed_plan *plan, const uint64_t *soff, cons
     const uint32_t N = plan->n, W = plan->band, n_q = (uint32_t)qlen.size();
     const unsigned threads =
         (unsigned)std::max<uint64_t>(256, std::min<uint64_t>(256 * 1024, (1ULL << 28) / (2ULL * W + 1)) / 256 * 256);
-    DevBuf &scr = plan->ctx->buf[15];
-    NMZ_TRY(scr.ensure(Carve::bytes_for(n_q + 1, 8) + Carve::bytes_for(n_q + 1, 4) +
-                       Carve::bytes_for((uint64_t)(2 * W + 1) * threads, 4)));
-    Carve cv(scr.ptr);
-    uint64_t *d_qstart = cv.take<uint64_t>(n_q + 1);
-    uint32_t *d_qlen = cv.take<uint32_t>(n_q + 1);
-    uint32_t *d_row = cv.take<uint32_t>((uint64_t)(2 * W + 1) * threads);
-    NMZ_HIP(hipMemcpyAsync(d_qstart, qstart.data(), n_q * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_qlen, qlen.data(), n_q * 4, hipMemcpyHostToDevice, st));
+    uint64_t *d_qstart;
+    uint32_t *d_qlen, *d_row;
+    ScratchLayout lay;
+    lay.add(&d_qstart, n_q + 1).add(&d_qlen, n_q + 1).add(&d_row, (uint64_t)(2 * W + 1) * threads);
+    NMZ_TRY(lay.bind(plan->ctx->buf[SLOT_ED_QUERY_GENERIC]));
+    NMZ_TRY(copy_h2d(d_qstart, qstart.data(), n_q, st));
+    NMZ_TRY(copy_h2d(d_qlen, qlen.data(), n_q, st));
     KernelTimer kt(plan->ctx, st, "ed_query_generic");
     hipLaunchKernelGGL(k_ed_query_generic, dim3(threads / 256), dim3(256), 0, st, soff, slen, sym, wide_sym, d_qstart,
                        d_qlen, d_qs, n_q, N, W, k, d_row, d_knn);
@@ -85,10 +83,10 @@ static int ed_query_bv(nmz_ed_plan *plan, const uint64_t *q_off, const uint64_t 
                     ++qd[q];
                 }
     }
-    DevBuf &scr = plan->ctx->buf[13];
-    NMZ_TRY(scr.ensure(Carve::bytes_for(qs.size(), 2)));
-    uint16_t *d_qs = scr.as<uint16_t>();
-    NMZ_HIP(hipMemcpyAsync(d_qs, qs.data(), qs.size() * 2, hipMemcpyHostToDevice, st));
+    uint16_t *d_qs;
+    ScratchLayout lay;
+    NMZ_TRY(lay.add(&d_qs, qs.size()).bind(plan->ctx->buf[SLOT_ED_QUERY_FORM]));
+    NMZ_TRY(copy_h2d(d_qs, qs.data(), qs.size(), st));
     std::vector<uint32_t> spill;  // queries for the generic kernel
     // a pool of 256 stored traces per workgroup: one pass of lanes, ~N/256 workgroups
     const uint32_t pool = N >= 256u * 1024u ? 1024u : 256u;
@@ -167,14 +165,12 @@ static int ed_query_wide(nmz_ed_plan *plan, const uint64_t *q_off, const uint64_
     uint64_t maxq = 0;
     for (uint32_t q = 0; q < n_queries; ++q)
         maxq = std::max<uint64_t>(maxq, std::min<uint64_t>(q_off[q + 1] - q_off[q], plan->maxlen));
-    DevBuf &scr = plan->ctx->buf[13];
-    NMZ_TRY(scr.ensure(Carve::bytes_for(batch * tbl, 4) + Carve::bytes_for(batch * maxq + 64, 2) +
-                       Carve::bytes_for(batch + 1, 8) + Carve::bytes_for(batch, 4)));
-    Carve cv(scr.ptr);
-    uint32_t *d_tbl = cv.take<uint32_t>(batch * tbl);
-    uint16_t *d_ids = cv.take<uint16_t>(batch * maxq + 64);
-    uint64_t *d_qoff = cv.take<uint64_t>(batch + 1);
-    uint32_t *d_qlen = cv.take<uint32_t>(batch);
+    uint32_t *d_tbl, *d_qlen;
+    uint16_t *d_ids;
+    uint64_t *d_qoff;
+    ScratchLayout lay;
+    lay.add(&d_tbl, batch * tbl).add(&d_ids, batch * maxq + 64).add(&d_qoff, batch + 1).add(&d_qlen, batch);
+    NMZ_TRY(lay.bind(plan->ctx->buf[SLOT_ED_QUERY_FORM]));
     // queries [q0, q0 + nb), each within the tables
     auto run = [&](uint32_t q0, uint32_t nb) -> int {
         const uint64_t b0 = q_off[q0], nsym = q_off[q0 + nb] - b0;
@@ -184,9 +180,9 @@ static int ed_query_wide(nmz_ed_plan *plan, const uint64_t *q_off, const uint64_
         query_ids(plan, q_sym + b0, nsym, ids, (uint16_t)plan->n_sym);  // unseen: the spare row
         for (uint32_t q = 0; q <= nb; ++q) qo[q] = q_off[q0 + q] - b0;
         for (uint32_t q = 0; q < nb; ++q) ql[q] = (uint32_t)(qo[q + 1] - qo[q]);
-        if (nsym) NMZ_HIP(hipMemcpyAsync(d_ids, ids.data(), nsym * 2, hipMemcpyHostToDevice, st));
-        NMZ_HIP(hipMemcpyAsync(d_qoff, qo.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-        NMZ_HIP(hipMemcpyAsync(d_qlen, ql.data(), nb * 4, hipMemcpyHostToDevice, st));
+        NMZ_TRY(copy_h2d(d_ids, ids.data(), nsym, st));
+        NMZ_TRY(copy_h2d(d_qoff, qo.data(), nb + 1, st));
+        NMZ_TRY(copy_h2d(d_qlen, ql.data(), nb, st));
         NMZ_TRY(ed_wide_build_peq(d_ids, d_qoff, nb, ns1, ndw, plan->ww, d_tbl, st));
         EdWideArgs A = ed_wide_plan_args(plan, k);
         A.peq = nullptr;  // the queries' own tables (d_tbl), one more row than the store's alphabet
@@ -209,9 +205,11 @@ static int ed_query_wide(nmz_ed_plan *plan, const uint64_t *q_off, const uint64_
             query_ids(plan, q_sym + q_off[q], n, ids, 0xffff);
             DevBuf one;
             ScopedRelease rel{one};
-            NMZ_TRY(one.ensure(Carve::bytes_for(n + 1, 2)));
-            NMZ_HIP(hipMemcpyAsync(one.ptr, ids.data(), n * 2, hipMemcpyHostToDevice, st));
-            NMZ_TRY(ed_query_generic_launch(plan, plan->d_qoff, nullptr, plan->d_qsym, false, one.ptr,
+            uint16_t *d_one;
+            ScratchLayout one_lay;
+            NMZ_TRY(one_lay.add(&d_one, n + 1).bind(one));
+            NMZ_TRY(copy_h2d(d_one, ids.data(), n, st));
+            NMZ_TRY(ed_query_generic_launch(plan, plan->d_qoff, nullptr, plan->d_qsym, false, d_one,
                                             std::vector<uint64_t>{0}, std::vector<uint32_t>{(uint32_t)n},
                                             d_knn + (uint64_t)q * k, k));
         }
@@ -227,15 +225,20 @@ static int ed_query_generic(nmz_ed_plan *plan, const uint64_t *q_off, const uint
     const bool dense = plan->tile;  // dense u16 ids (unseen query symbols: 0xffff, never a stored id)
     static_assert(MAX_FAST_SYMBOLS <= 0xffff, "0xffff must not be a dense id");
     const uint64_t total = q_off[n_queries];
-    DevBuf &scr = plan->ctx->buf[13];
-    NMZ_TRY(scr.ensure(Carve::bytes_for(total + 1, dense ? 2 : 8)));
-    void *d_qs = scr.ptr;
+    // the queries' symbols: the one field is u16 ids on a dense plan, the u64 symbols themselves otherwise
+    uint16_t *d_ids = nullptr;
+    uint64_t *d_sym = nullptr;
+    ScratchLayout lay;
+    if (dense) lay.add(&d_ids, total + 1);
+    else lay.add(&d_sym, total + 1);
+    NMZ_TRY(lay.bind(plan->ctx->buf[SLOT_ED_QUERY_FORM]));
+    const void *d_qs = dense ? (const void *)d_ids : (const void *)d_sym;
     std::vector<uint16_t> ids;
     if (dense) {
         query_ids(plan, q_sym, total, ids, 0xffff);
-        if (total) NMZ_HIP(hipMemcpyAsync(d_qs, ids.data(), total * 2, hipMemcpyHostToDevice, st));
-    } else if (total) {
-        NMZ_HIP(hipMemcpyAsync(d_qs, q_sym, total * 8, hipMemcpyHostToDevice, st));
+        NMZ_TRY(copy_h2d(d_ids, ids.data(), total, st));
+    } else {
+        NMZ_TRY(copy_h2d(d_sym, q_sym, total, st));
     }
     std::vector<uint64_t> qstart(n_queries);
     std::vector<uint32_t> qlen(n_queries);
@@ -266,13 +269,14 @@ int nmz_ed_plan_query_knn(nmz_ed_plan *plan, const uint64_t *q_off, const uint64
     NMZ_CHECK(total == 0 || q_sym, "q_sym is NULL");
     for (uint32_t q = 0; q < n_queries; ++q) NMZ_CHECK(q_off[q] <= q_off[q + 1], "query offsets must not decrease");
     hipStream_t st = plan->ctx->stream;
+    HostCall call(plan->ctx);
     const uint32_t N = plan->n;
     const uint64_t nk = (uint64_t)n_queries * k;
-    DevBuf &scr = plan->ctx->buf[11];
-    NMZ_TRY(scr.ensure(Carve::bytes_for(nk, 8) + 2 * Carve::bytes_for(nk, 4)));
-    Carve cv(scr.ptr);
-    uint64_t *d_knn = cv.take<uint64_t>(nk);
-    uint32_t *d_id = cv.take<uint32_t>(nk), *d_ds = cv.take<uint32_t>(nk);
+    uint64_t *d_knn;
+    uint32_t *d_id, *d_ds;
+    ScratchLayout lay;
+    lay.add(&d_knn, nk).add(&d_id, nk).add(&d_ds, nk);
+    NMZ_TRY(lay.bind(plan->ctx->buf[SLOT_KNN_LISTS_OR_TRACE_RINGS]));
     knn_init_launch(d_knn, nk, st);
     if (N) {
         if (plan->bv) NMZ_TRY(ed_query_bv(plan, q_off, q_sym, n_queries, k, d_knn));
@@ -281,7 +285,7 @@ int nmz_ed_plan_query_knn(nmz_ed_plan *plan, const uint64_t *q_off, const uint64
     }
     // the query kernels list in-band results only: every other stored trace is at band + 1
     knn_fill_launch(d_knn, n_queries, k, N, plan->band + 1, 0, st);
-    return knn_final_to_host(d_knn, nk, d_id, d_ds, knn_id, knn_dist, st);
+    return knn_final_to_host(call, d_knn, nk, d_id, d_ds, knn_id, knn_dist);
 }
 
 }  // extern "C"

@@ -332,21 +332,14 @@ struct TpSearch {
         // scratch: {mismatch flag, record count out}, the entry total, the offset kernels' block sums, the records'
         // per-stripe counts, the per-pair counts (zero between searches: the write pass takes back what the count pass
         // added) and offsets
-        const size_t tp_bytes = Carve::bytes_for(4, 4) + Carve::bytes_for(1, 8) + Carve::bytes_for(2 * TP_MAX_BLOCKS, 8) +
-                                Carve::bytes_for(ED_REC_STRIPES, 4) + 3 * Carve::bytes_for(n_pairs + 1, 4);
+        ScratchLayout lay;
+        lay.add(&f, 4).add(&d_tot64, 1).add(&d_agg, 2 * TP_MAX_BLOCKS).add(&d_rec_cnt, ED_REC_STRIPES);
+        lay.add(&d_cnt, n_pairs + 1).add(&d_poff, n_pairs + 1).add(&d_ioff, n_pairs + 1);
         // an earlier search of this plan whose sizes contradicted the cache is reported here (without waiting for it)
         NMZ_TRY(ed_tp_flag_check(p, false, st));
-        NMZ_TRY(p->tp_mem.ensure(tp_bytes));
-        Carve cv(p->tp_mem.ptr);
-        f = cv.take<uint32_t>(4);
-        d_tot64 = cv.take<uint64_t>(1);
-        d_agg = cv.take<uint64_t>(2 * TP_MAX_BLOCKS);
-        d_rec_cnt = cv.take<uint32_t>(ED_REC_STRIPES);
-        d_cnt = cv.take<uint32_t>(n_pairs + 1);
-        d_poff = cv.take<uint32_t>(n_pairs + 1);
-        d_ioff = cv.take<uint32_t>(n_pairs + 1);
+        NMZ_TRY(lay.bind(p->tp_mem));
         if (p->tp_mem.gen != p->tp_mem_gen || f != p->d_tp_mismatch) {  // a new scratch buffer: flag and counts clear
-            NMZ_HIP(hipMemsetAsync(p->tp_mem.ptr, 0, tp_bytes, st));
+            NMZ_HIP(hipMemsetAsync(p->tp_mem.ptr, 0, lay.bytes(), st));
             p->d_tp_mismatch = f;
             p->tp_mem_gen = p->tp_mem.gen;
         } else if (p->tp_dirty) {  // an earlier search stopped between its count and write passes
@@ -371,12 +364,15 @@ struct TpSearch {
         const char *rc_env = ab_env("NMZ_ED_QG_RECOMPUTE");
         // (the kernels count records with a u32 atomic, up to 128 per tile: a launch that could pass 2^32 of them would
         // wrap the counter, so such searches recompute instead)
+        uint4 *d_rec = nullptr;  // one field of bytes, addressed in 16-byte records
+        ScratchLayout rec_lay;
         if (!(rc_env && atoi(rc_env) == 1) && n_tiles_all * 128 < (1ULL << 32) &&
-            p->tp_rec.ensure(Carve::bytes_for(REC_CTR_BYTES + rec_share * ED_REC_STRIPES * 32, 1)) == NMZ_OK) {
-            Q.recs = p->tp_rec.as<uint4>() + REC_CTR_BYTES / 16;
+            rec_lay.add(&d_rec, (REC_CTR_BYTES + rec_share * ED_REC_STRIPES * 32) / 16).bind(p->tp_rec) == NMZ_OK) {
+            Q.recs = d_rec + REC_CTR_BYTES / 16;
             Q.rec_cap = (uint32_t)rec_share;
         }
-        Q.n_rec = Q.recs ? p->tp_rec.as<uint32_t>() : nullptr;  // the stripe counters, at the buffer's start
+        // the stripe counters, at the buffer's start
+        Q.n_rec = Q.recs ? reinterpret_cast<uint32_t *>(d_rec) : nullptr;
         // (k_tp_scan leaves them at zero; a new allocation -- tp_rec's generation changed, whatever its address -- or
         // an interrupted search clears them here)
         if (Q.n_rec && (p->tp_rec.gen != p->tp_rec_gen || p->tp_dirty)) {
@@ -449,8 +445,8 @@ struct TpSearch {
     int write_dp(uint64_t n_ent, uint32_t n_items) {
         // the u32 scans (entry and item offsets) hold only below 2^32 entries: a batch must never reach it
         NMZ_CHECK(n_ent < (1ULL << 32), "internal: a two-phase batch reaches 2^32 entries");
-        NMZ_TRY(p->tp_ent.ensure(Carve::bytes_for(n_ent + 1, 4)));
-        Q.ent = p->tp_ent.as<uint32_t>();
+        ScratchLayout lay;
+        NMZ_TRY(lay.add(&Q.ent, n_ent + 1).bind(p->tp_ent));
         Q.ent_cap = n_ent;  // entry writes past the sizes the lists were made for are dropped
         {
             KernelTimer kt(p->ctx, st, "ed_qg_filter");
@@ -526,11 +522,13 @@ static int tp_batched(TpSearch &S, const uint64_t *tl, uint64_t n_tiles_all, uin
             NMZ_CHECK(a < (1ULL << 32), "one query block's candidate entries reach 2^32 (too many traces)");
             std::vector<uint64_t> tiles;
             superblock_tiles(qbs, j0, j1, S.Q.NCB, &tiles);
-            NMZ_TRY(sub.ensure(Carve::bytes_for(tiles.size() + 1, 8)));
+            uint64_t *d_tiles;
+            ScratchLayout lay;
+            NMZ_TRY(lay.add(&d_tiles, tiles.size() + 1).bind(sub));
             NMZ_HIP(hipStreamSynchronize(st));  // the previous sub-batch's kernels have read the list
-            if (!tiles.empty())
-                NMZ_HIP(hipMemcpy(sub.ptr, tiles.data(), tiles.size() * 8, hipMemcpyHostToDevice));
-            NMZ_TRY(S.count(sub.as<uint64_t>(), tiles.size()));
+            if (!tiles.empty())  // synchronous: the list is pageable and reused at once
+                NMZ_HIP(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+            NMZ_TRY(S.count(d_tiles, tiles.size()));
             NMZ_TRY(S.write_dp(S.tot64, S.tot_items));
             j0 = j1;
         }
@@ -554,8 +552,11 @@ int ed_bv_two_phase(nmz_ed_plan *p, hipStream_t st, EdBvArgs &A, uint64_t *d_knn
         std::vector<uint32_t> qbs, grp;
         std::vector<uint64_t> tiles;
         shard_tiles((N + 63) / 64, (N + 255) / 256, A.shard, A.n_shards, qbs, grp, &tiles);
-        NMZ_TRY(tl.ensure(Carve::bytes_for(tiles.size() + 1, 8)));
-        if (!tiles.empty()) NMZ_HIP(hipMemcpy(tl.ptr, tiles.data(), tiles.size() * 8, hipMemcpyHostToDevice));
+        uint64_t *d_tiles;
+        ScratchLayout lay;
+        NMZ_TRY(lay.add(&d_tiles, tiles.size() + 1).bind(tl));
+        if (!tiles.empty())  // synchronous: the list is pageable
+            NMZ_HIP(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         p->tile_count[key] = tiles.size();
     }
     const uint64_t n_tiles_all = p->tile_count[key];

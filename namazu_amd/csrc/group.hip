@@ -95,12 +95,15 @@ class DeviceWorker {
 // words per rank of the status / fingerprint exchange (a status word + nmz_ed_plan_fingerprint's words)
 constexpr size_t XW_WORDS = 1 + NMZ_ED_FP_WORDS;
 
+// a member's group scratch: the exchange (send | recv), the merge scratch, the shard outputs
+enum GroupBuf : int { GB_EXCHANGE, GB_MERGE, GB_SHARD, GB_COUNT };
+
 struct GroupMember {
     nmz_ctx *ctx = nullptr;
     int rank = 0;
     ncclComm_t comm = nullptr;
     std::unique_ptr<DeviceWorker> worker;
-    DevBuf buf[4];  // group scratch on this device: [0] exchange (send | recv), [1] merge scratch, [2] shard outputs
+    DevBuf buf[GB_COUNT];  // group scratch on this device
     // the status exchange, allocated at group open: device send [XW_WORDS] | recv [n_ranks][XW_WORDS], and pinned
     // host staging of the same layout
     DevBuf xw;
@@ -320,11 +323,10 @@ static int group_topk_exchange(nmz_group *g, uint32_t k, const std::vector<nmz_t
         if (sweep_st[i] != NMZ_OK) return fail(sweep_st[i], sweep_msg[i]);  // the sweep failed here: nothing to merge
         GroupMember &mb = g->m[i];
         NMZ_TRY(injected(mb, "topk"));
-        const size_t lb = Carve::bytes_for(k, sizeof(nmz_topk_entry));
-        NMZ_TRY(mb.buf[0].ensure(lb + Carve::bytes_for(R * k, sizeof(nmz_topk_entry))));
-        NMZ_TRY(mb.buf[1].ensure(Carve::bytes_for(std::max<size_t>(R, n_local[i]) * k + k, sizeof(nmz_topk_entry))));
-        Carve cv(mb.buf[0].ptr);
-        nmz_topk_entry *s = cv.take<nmz_topk_entry>(k), *r = cv.take<nmz_topk_entry>(R * k);
+        nmz_topk_entry *s, *r, *merge;
+        ScratchLayout xl, ml;
+        NMZ_TRY(xl.add(&s, k).add(&r, R * k).bind(mb.buf[GB_EXCHANGE]));
+        NMZ_TRY(ml.add(&merge, std::max<size_t>(R, n_local[i]) * k + k).bind(mb.buf[GB_MERGE]));
         send[i] = s;
         recv[i] = r;
         hipStream_t st = mb.ctx->stream;
@@ -335,7 +337,7 @@ static int group_topk_exchange(nmz_group *g, uint32_t k, const std::vector<nmz_t
             NMZ_HIP(hipStreamSynchronize(st));  // pageable source
             return NMZ_OK;
         }
-        return topk_merge_lists(st, lists[i], mb.buf[1].as<nmz_topk_entry>(), n_local[i], k, s);
+        return topk_merge_lists(st, lists[i], merge, n_local[i], k, s);
     });
     NMZ_TRY(group_agree_status(g, st2, msg2, "the sweep"));
     NMZ_TRY(group_allgather(g, send, recv, (size_t)k * sizeof(nmz_topk_entry)));
@@ -343,11 +345,11 @@ static int group_topk_exchange(nmz_group *g, uint32_t k, const std::vector<nmz_t
         if (!reports(g, i)) return NMZ_OK;
         GroupMember &mb = g->m[i];
         hipStream_t st = mb.ctx->stream;
-        nmz_topk_entry *fin = mb.buf[1].as<nmz_topk_entry>() + R * k;
+        nmz_topk_entry *merge = mb.buf[GB_MERGE].as<nmz_topk_entry>(), *fin = merge + R * k;
         // topk_merge_lists overwrites both of its buffers: merge from a copy of the gathered lists
         nmz_topk_entry *a = (nmz_topk_entry *)recv[i];
-        NMZ_TRY(topk_merge_lists(st, a, mb.buf[1].as<nmz_topk_entry>(), R, k, fin));
-        NMZ_HIP(hipMemcpyAsync(topk, fin, k * sizeof(nmz_topk_entry), hipMemcpyDeviceToHost, st));
+        NMZ_TRY(topk_merge_lists(st, a, merge, R, k, fin));
+        NMZ_TRY(copy_d2h(topk, fin, k, st));
         NMZ_HIP(hipStreamSynchronize(st));
         return NMZ_OK;
     });
@@ -384,12 +386,9 @@ struct ShardOut {
     nmz_topk_entry *lists;
 };
 static int shard_out(GroupMember &mb, uint64_t max_shard, uint32_t n_local, uint32_t k, ShardOut &o) {
-    NMZ_TRY(mb.buf[2].ensure(Carve::bytes_for(max_shard + 1, sizeof(nmz_sched_stats)) +
-                             Carve::bytes_for((uint64_t)std::max(n_local, 1u) * k + 1, sizeof(nmz_topk_entry))));
-    Carve cv(mb.buf[2].ptr);
-    o.stats = cv.take<nmz_sched_stats>(max_shard + 1);
-    o.lists = cv.take<nmz_topk_entry>((uint64_t)std::max(n_local, 1u) * k + 1);
-    return NMZ_OK;
+    ScratchLayout lay;
+    lay.add(&o.stats, max_shard + 1).add(&o.lists, (uint64_t)std::max(n_local, 1u) * k + 1);
+    return lay.bind(mb.buf[GB_SHARD]);
 }
 
 // One sweep over the group: for every local shard, sweep(member, plan index, lo, n, d_stats, d_topk_list) on
@@ -630,13 +629,12 @@ int nmz_replayable_group_sweep(nmz_replayable_group_plan *gp, const uint32_t *se
                            const uint32_t b0 = seed_off[lo], b1 = seed_off[lo + n];
                            std::vector<uint32_t> off(n + 1);
                            for (uint64_t t = 0; t <= n; ++t) off[t] = seed_off[lo + t] - b0;
-                           NMZ_TRY(seeds[i].ensure(Carve::bytes_for(n + 1, 4) + Carve::bytes_for(b1 - b0 + 1, 1)));
-                           Carve cv(seeds[i].ptr);
-                           uint32_t *d_off = cv.take<uint32_t>(n + 1);
-                           uint8_t *d_b = cv.take<uint8_t>(b1 - b0 + 1);
-                           NMZ_HIP(hipMemcpyAsync(d_off, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
-                           if (b1 > b0)
-                               NMZ_HIP(hipMemcpyAsync(d_b, seed_bytes + b0, b1 - b0, hipMemcpyHostToDevice, st));
+                           uint32_t *d_off;
+                           uint8_t *d_b;
+                           ScratchLayout lay;
+                           NMZ_TRY(lay.add(&d_off, n + 1).add(&d_b, b1 - b0 + 1).bind(seeds[i]));
+                           NMZ_TRY(copy_h2d(d_off, off.data(), n + 1, st));
+                           NMZ_TRY(copy_h2d(d_b, seed_bytes + b0, b1 - b0, st));
                            if (k)
                                NMZ_TRY(nmz_replayable_sweep_topk_dev(gp->p[i], d_off, d_b, n, lo, k, d_stats, d_topk,
                                                                      nullptr));
@@ -790,8 +788,9 @@ int nmz_ed_group_plan_create_opts(nmz_group *g, const uint64_t *off, const uint6
             const auto t0 = clk::now();
             GroupMember &mb = g->m[i];
             hipStream_t stm = mb.ctx->stream;
-            NMZ_TRY(full[i].ensure(Carve::bytes_for(share * R, 8)));
-            uint64_t *d = full[i].as<uint64_t>();
+            uint64_t *d;
+            ScratchLayout lay;
+            NMZ_TRY(lay.add(&d, share * R).bind(full[i]));
             const uint64_t lo = std::min<uint64_t>((uint64_t)mb.rank * share, total);
             const uint64_t hi = std::min<uint64_t>(lo + share, total);
             if (hi > lo)
@@ -899,14 +898,15 @@ int nmz_ed_group_allpairs_knn(nmz_ed_group_plan *gp, uint32_t k, uint32_t *knn_i
         NMZ_TRY(injected(mb, "ed_search"));
         const std::vector<uint32_t> mine = shards_of(g, mb.rank);
         const uint64_t nl = std::max<size_t>(mine.size(), 1);
-        NMZ_TRY(mb.buf[0].ensure(Carve::bytes_for(nk, 8) * (1 + R)));
-        NMZ_TRY(mb.buf[2].ensure(Carve::bytes_for(nk * nl, 8) + Carve::bytes_for(nk, 8) * 2));
-        Carve c0(mb.buf[0].ptr);
-        send[i] = c0.take<uint64_t>(nk);
-        recv[i] = c0.take<uint64_t>(nk * R);
-        Carve c2(mb.buf[2].ptr);
-        uint64_t *parts = c2.take<uint64_t>(nk * nl);
-        tmp[i] = c2.take<uint64_t>(nk);
+        // the exchange buffer's size counts each of the R gathered lists rounded up to 256 bytes by itself (32 keys),
+        // though they lie packed; the shard buffer has room for one more list than the merge takes. Both only keep
+        // the old size arithmetic byte for byte and can go once sizes may change
+        uint64_t *d_send, *d_recv, *parts, *spare;
+        ScratchLayout xl, sl;
+        NMZ_TRY(xl.add(&d_send, nk).add(&d_recv, ((nk + 31) & ~uint64_t(31)) * R).bind(mb.buf[GB_EXCHANGE]));
+        NMZ_TRY(sl.add(&parts, nk * nl).add(&tmp[i], nk).add(&spare, nk).bind(mb.buf[GB_SHARD]));
+        send[i] = d_send;
+        recv[i] = d_recv;
         hipStream_t st = mb.ctx->stream;
         if (mine.empty()) {  // no shard here: empty lists
             NMZ_HIP(hipMemsetAsync(send[i], 0xff, nk * 8, st));

@@ -266,15 +266,14 @@ static int match_plan_create_locked(nmz_ctx *ctx, const uint64_t *sym, const int
     p->mem.pool = &ctx->pool;
     p->n_events = E;
     p->n_symbols = U;
-    int rc = p->mem.ensure(Carve::bytes_for(U, 8) + Carve::bytes_for(U + 1, 2) + Carve::bytes_for(E, 2));
+    uint64_t *d_usym;
+    uint16_t *d_start, *d_ev;
+    ScratchLayout lay;
+    int rc = lay.add(&d_usym, U).add(&d_start, U + 1).add(&d_ev, E).bind(p->mem);
     if (rc != NMZ_OK) {
         delete p;
         return rc;
     }
-    Carve cv(p->mem.ptr);
-    uint64_t *d_usym = cv.take<uint64_t>(U);
-    uint16_t *d_start = cv.take<uint16_t>(U + 1);
-    uint16_t *d_ev = cv.take<uint16_t>(E);
     p->args = MtArgs{d_usym, d_start, d_ev, E, U, nullptr, nullptr, 0, nullptr, 0};
     hipStream_t st = ctx->stream;
     hipError_t e = hipMemcpyAsync(d_usym, usym.data(), (size_t)U * 8, hipMemcpyHostToDevice, st);
@@ -330,26 +329,17 @@ static int match_enqueue(nmz_match_plan *p, hipStream_t st, const uint64_t *d_ru
     return rc;
 }
 
-MatchCall::~MatchCall() {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (plan) match_plan_destroy_locked(plan);
-    work.release();
-}
-
-int MatchCall::run(const uint64_t *sym, const int64_t *arrival, uint32_t E, const uint64_t *run_off,
-                   const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos) {
+int match_call(nmz_ctx *ctx, HostCall &call, const uint64_t *sym, const int64_t *arrival, uint32_t E,
+               const uint64_t *run_off, const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos) {
+    nmz_match_plan *plan = nullptr;
     NMZ_TRY(match_plan_create_locked(ctx, sym, arrival, E, &plan));
-    hipStream_t st = ctx->stream;
-    const uint64_t total = run_off[n_runs];
-    const size_t cells = (size_t)n_runs * E;
-    NMZ_TRY(work.ensure(Carve::bytes_for(cells, 4) + Carve::bytes_for(n_runs + 1, 8) + Carve::bytes_for(total + 1, 8)));
-    Carve cv(work.ptr);
-    *d_pos = cv.take<uint32_t>(cells);
-    uint64_t *d_off = cv.take<uint64_t>(n_runs + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    NMZ_HIP(hipMemcpyAsync(d_off, run_off, (n_runs + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, run_sym, total * 8, hipMemcpyHostToDevice, st));
-    return match_enqueue(plan, st, d_off, d_sym, n_runs, *d_pos);
+    call.own_plan<match_plan_destroy_locked>(plan);
+    uint64_t *d_off, *d_sym;
+    ScratchLayout lay;
+    lay.add(d_pos, (size_t)n_runs * E).add(&d_off, n_runs + 1).add(&d_sym, run_off[n_runs] + 1);
+    NMZ_TRY(lay.bind(call.work));
+    NMZ_TRY(upload_csr(d_off, d_sym, run_off, run_sym, n_runs, call.st));
+    return match_enqueue(plan, call.st, d_off, d_sym, n_runs, *d_pos);
 }
 
 }  // namespace nmz
@@ -425,12 +415,11 @@ int nmz_match_runs(nmz_ctx *ctx, const uint64_t *sym, const int64_t *arrival_ns,
     NMZ_CHECK(ctx != nullptr, "ctx is NULL");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
-    MatchCall call(ctx);
+    HostCall call(ctx);
     uint32_t *d_pos = nullptr;
-    NMZ_TRY(call.run(sym, arrival_ns, n_events, run_off, run_sym, n_runs, &d_pos));
-    NMZ_HIP(hipMemcpyAsync(pos, d_pos, (size_t)n_runs * n_events * 4, hipMemcpyDeviceToHost, ctx->stream));
-    NMZ_HIP(hipStreamSynchronize(ctx->stream));
-    return NMZ_OK;
+    NMZ_TRY(match_call(ctx, call, sym, arrival_ns, n_events, run_off, run_sym, n_runs, &d_pos));
+    NMZ_TRY(copy_d2h(pos, d_pos, (size_t)n_runs * n_events, call.st));
+    return call.done();
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/nmz_gpu.h"
+#include "scratch_layout.h"
 
 // ---------------------------------------------------------------------------
 // error plumbing (thread-local message, int status codes of nmz_gpu.h)
@@ -45,6 +46,10 @@ struct DevBuf {
     size_t cap = 0;
     std::vector<DevBuf> *pool = nullptr;
     uint64_t gen = 0;  // bumped whenever ensure() hands out a different allocation (its contents are then undefined)
+    // a context slot's name and in-use mark (ScratchLayout::bind sets it for the layout's lifetime and refuses a
+    // marked slot); plan-owned and pool-backed buffers have no name and are never marked
+    const char *slot = nullptr;
+    bool busy = false;
     int ensure(size_t bytes);
     void release();
     template <typename T>
@@ -62,6 +67,58 @@ struct HostPin {
     int ensure(size_t bytes);   // waits for that copy, then grows (a power of two of at least 1 MiB)
     int mark(hipStream_t st);
     void release();
+};
+
+// ---------------------------------------------------------------------------
+// The context's scratch slots (nmz_ctx::buf). One enumerator per role. Two roles share a slot only where they can
+// never be live in the same call; a slot bound twice in one call is refused by ScratchLayout::bind (NMZ_EINVAL).
+// SLOT_TOPK alone is sized by a plain ensure() (one field plus a spare 256 bytes, which no layout's rounding gives)
+// and so never carries the in-use mark.
+// Live together, so their slots must stay distinct:
+//   * SLOT_CONTRAST_HOST (nmz_order_contrast_runs), SLOT_CONTRAST_RUN (contrast_run) and match_call's pool buffer
+//     (HostCall::work)
+//   * SLOT_TARGET_DELIVERY_HOST (the delivery host form), SLOT_DELIVERY_CLASSES, SLOT_CLASSES (classes_launch)
+//     and the rank-key table (nmz_ctx::rank_keys)
+//   * SLOT_KNN_LISTS_OR_TRACE_RINGS (nmz_ed_plan_query_knn), SLOT_ED_QUERY_FORM (ed_query_bv) and its spill into
+//     ed_query_generic_launch (SLOT_ED_QUERY_GENERIC)
+// ---------------------------------------------------------------------------
+#define NMZ_SLOTS(X)                                                                                                  \
+    /* the order sweep's and the replayable sweep's host forms: each is one synchronous call holding the context */   \
+    X(SLOT_SWEEP_HOST)                                                                                                \
+    /* nmz_random_sweep and nmz_procset_sweep: host forms, one synchronous call each */                               \
+    X(SLOT_RANDOM_PROCSET_SWEEP)                                                                                      \
+    X(SLOT_ED_KNN_HOST)      /* nmz_ed_allpairs_knn: the lists and their ids and distances */                         \
+    X(SLOT_ED_KNN)           /* ed_knn_run's generic fallback: a chunk of pairs, distances, DP rows */                \
+    X(SLOT_ED_PAIRS_HOST)    /* nmz_ed_pairs */                                                                       \
+    X(SLOT_TOPK)             /* nmz_topk_select_dev */                                                                \
+    X(SLOT_CLASSES)          /* classes_launch: sort keys and payloads */                                             \
+    X(SLOT_UNIQUE_HOST)      /* nmz_trace_signatures / nmz_unique_traces host forms */                                \
+    X(SLOT_REPLAYABLE_DECIDE) /* nmz_replayable_decide */                                                             \
+    /* nmz_random_decide and nmz_procset_decide: host forms, one synchronous call each */                             \
+    X(SLOT_RANDOM_PROCSET_DECIDE)                                                                                     \
+    X(SLOT_PLAN_TMP)         /* replayable plan creation: the wide-table build's temporary */                         \
+    /* ed_query's ids and the replayable traces sweep's result rings: an ed plan query never runs inside a sweep */   \
+    X(SLOT_KNN_LISTS_OR_TRACE_RINGS)                                                                                  \
+    X(SLOT_FNV_BATCH)        /* nmz_fnv1a64_batch */                                                                  \
+    /* ed_query_bv, ed_query_wide or ed_query_generic: the plan's kind picks one of them per call */                  \
+    X(SLOT_ED_QUERY_FORM)                                                                                             \
+    X(SLOT_ED_QUERY_GENERIC) /* ed_query_generic_launch, also as ed_query_bv's spill */                               \
+    /* the target and the delivery sweeps' host forms: each is one synchronous call holding the context */            \
+    X(SLOT_TARGET_DELIVERY_HOST)                                                                                      \
+    X(SLOT_DELIVERY_CLASSES) /* delivery_classes_locked: signatures and best gaps */                                  \
+    X(SLOT_CONTRAST_RUN)     /* contrast_run: the run order, the merged list, the per-workgroup lists */              \
+    /* nmz_order_contrast and nmz_order_contrast_runs: host forms, one synchronous call each */                       \
+    X(SLOT_CONTRAST_HOST)
+enum Slot : int {
+#define X(name) name,
+    NMZ_SLOTS(X)
+#undef X
+    SLOT_COUNT
+};
+constexpr const char *SLOT_NAMES[SLOT_COUNT] = {
+#define X(name) #name,
+    NMZ_SLOTS(X)
+#undef X
 };
 
 }  // namespace nmz
@@ -85,7 +142,8 @@ struct nmz_ctx {
     std::mutex mu;
     int n_cu = 0;
     // scratch slots reused across calls (host-pointer entry points)
-    nmz::DevBuf buf[20];
+    nmz::DevBuf buf[nmz::SLOT_COUNT];  // indexed by nmz::Slot
+    nmz::DevBuf rank_keys;  // the signature's rank-key table (sig_rank_keys), built once per context; not scratch
     std::vector<nmz::DevBuf> pool;  // free plan buffers (DevBuf::pool), freed by nmz_close
     nmz::HostPin pin[2];             // pinned staging of plan inputs ([0] replayable plan, [1] its wavelet classes)
     bool wt_lds_attr = false;        // the wavelet-tree kernels' LDS attribute is set on this context's device
@@ -95,6 +153,9 @@ struct nmz_ctx {
     hipEvent_t sweep_ev[3] = {nullptr, nullptr, nullptr};
     nmz::HostPin tkpin;
     NmzTiming timing;
+    nmz_ctx() {
+        for (int i = 0; i < nmz::SLOT_COUNT; ++i) buf[i].slot = nmz::SLOT_NAMES[i];
+    }
 };
 
 namespace nmz {
@@ -133,6 +194,70 @@ struct CtxGuard {
     int rc = NMZ_OK;
     explicit CtxGuard(nmz_ctx *c) : lk(c->mu) {
         if (hipSetDevice(c->device) != hipSuccess) rc = fail(NMZ_EHIP, "hipSetDevice failed");
+    }
+};
+
+// Typed asynchronous copies: the byte count comes from the pointers' type, in size_t; a count of 0 copies nothing.
+// A destination / source type mismatch does not compile.
+template <typename T>
+inline int copy_h2d(T *d_dst, const T *src, size_t count, hipStream_t st) {
+    if (count) NMZ_HIP(hipMemcpyAsync(d_dst, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return NMZ_OK;
+}
+template <typename T>
+inline int copy_d2h(T *dst, const T *d_src, size_t count, hipStream_t st) {
+    if (count) NMZ_HIP(hipMemcpyAsync(dst, d_src, count * sizeof(T), hipMemcpyDeviceToHost, st));
+    return NMZ_OK;
+}
+// the CSR of n traces: off[n + 1], then sym[off[n]]
+inline int upload_csr(uint64_t *d_off, uint64_t *d_sym, const uint64_t *off, const uint64_t *sym, uint64_t n,
+                      hipStream_t st) {
+    NMZ_TRY(copy_h2d(d_off, off, n + 1, st));
+    return copy_h2d(d_sym, sym, off[n], st);
+}
+// The seed strings of a host sweep. seed_csr_bytes: the bytes of seed_bytes (none in the decimal form, whose
+// seeds are numbers); upload_seeds: seed_off[n_seeds + 1] and the bytes, nothing in the decimal form.
+inline int seed_csr_bytes(const uint32_t *seed_off, const uint8_t *seed_bytes, uint64_t n_seeds, bool decimal,
+                          uint64_t *sbytes) {
+    *sbytes = (!decimal && n_seeds) ? seed_off[n_seeds] : 0;
+    NMZ_CHECK(*sbytes == 0 || seed_bytes, "seed_bytes is NULL");
+    return NMZ_OK;
+}
+inline int upload_seeds(uint32_t *d_soff, uint8_t *d_sb, const uint32_t *seed_off, const uint8_t *seed_bytes,
+                        uint64_t n_seeds, bool decimal, hipStream_t st) {
+    if (decimal || !n_seeds) return NMZ_OK;
+    NMZ_TRY(copy_h2d(d_soff, seed_off, n_seeds + 1, st));
+    return copy_h2d(d_sb, seed_bytes, seed_off[n_seeds], st);
+}
+
+// RAII: one synchronous host-form call on a context's stream. Declare it after the host-side variables that the
+// call's device-to-host copies write and before anything else: every exit path then drains the stream before
+// those variables (and the caller's arrays) go out of scope. After the drain it destroys the call's plan, if it
+// owns one, and then hands `work`, the call's buffer from the context's pool (if the call took one), back to the
+// pool. done() is the success path's one hipStreamSynchronize: it returns that status and disarms the drain.
+struct HostCall {
+    hipStream_t st;
+    bool armed = true;
+    void *plan = nullptr;
+    void (*destroy)(void *) = nullptr;
+    DevBuf work;
+    explicit HostCall(nmz_ctx *c) : st(c->stream) { work.pool = &c->pool; }
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    template <auto Destroy, typename P>
+    void own_plan(P *p) {
+        plan = p;
+        destroy = [](void *q) { (void)Destroy(static_cast<P *>(q)); };
+    }
+    int done() {
+        armed = false;
+        NMZ_HIP(hipStreamSynchronize(st));
+        return NMZ_OK;
+    }
+    ~HostCall() {
+        if (armed) (void)hipStreamSynchronize(st);
+        if (plan) destroy(plan);
+        work.release();
     }
 };
 

@@ -367,6 +367,7 @@ int nmz_close(nmz_ctx *ctx) {
             if (ctx->sweep_ev[i]) (void)hipEventDestroy(ctx->sweep_ev[i]);
         ctx->tkpin.release();
         for (auto &b : ctx->buf) b.release();
+        ctx->rank_keys.release();
         for (auto &b : ctx->pin) b.release();
         for (auto &b : ctx->pool) (void)hipFree(b.ptr);
         ctx->pool.clear();
@@ -501,17 +502,18 @@ int nmz_fnv1a64_batch(nmz_ctx *ctx, const uint64_t *off, const uint8_t *bytes, u
     const uint64_t nb = off[n];
     NMZ_CHECK(nb == 0 || bytes, "bytes is NULL");
     hipStream_t st = ctx->stream;
-    NMZ_TRY(ctx->buf[12].ensure(Carve::bytes_for(n + 1, 8) * 2 + Carve::bytes_for(nb + 1, 1)));
-    Carve cv(ctx->buf[12].ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n + 1), *d_out = cv.take<uint64_t>(n + 1);
-    uint8_t *d_b = cv.take<uint8_t>(nb + 1);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (nb) NMZ_HIP(hipMemcpyAsync(d_b, bytes, nb, hipMemcpyHostToDevice, st));
+    HostCall call(ctx);
+    uint64_t *d_off, *d_out;
+    uint8_t *d_b;
+    ScratchLayout lay;
+    lay.add(&d_off, n + 1).add(&d_out, n + 1).add(&d_b, nb + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_FNV_BATCH]));
+    NMZ_TRY(copy_h2d(d_off, off, n + 1, st));
+    NMZ_TRY(copy_h2d(d_b, bytes, nb, st));
     hipLaunchKernelGGL(k_fnv_batch, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_off, d_b, n, d_out);
     NMZ_HIP(hipGetLastError());
-    NMZ_HIP(hipMemcpyAsync(out, d_out, n * 8, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    NMZ_TRY(copy_d2h(out, d_out, n, st));
+    return call.done();
 }
 
 int nmz_fnv1a64_batch_host(const uint64_t *off, const uint8_t *bytes, uint64_t n, uint64_t *out) {

@@ -10,44 +10,23 @@ int topk_merge_lists(hipStream_t st, nmz_topk_entry *a, nmz_topk_entry *b, uint6
 int topk_select(hipStream_t st, const nmz_sched_stats *d_stats, uint64_t n, uint64_t seed0, uint32_t k,
                 nmz_topk_entry *d_scratch, nmz_topk_entry *d_out);
 
-// scratch carving helper: bump allocator over one device buffer (256-B aligned)
-struct Carve {
-    char *base;
-    size_t off = 0;
-    explicit Carve(void *p) : base(static_cast<char *>(p)) {}
-    template <typename T>
-    T *take(size_t count) {
-        T *p = reinterpret_cast<T *>(base + off);
-        off += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-    static size_t bytes_for(size_t count, size_t elem) { return (count * elem + 255) & ~size_t(255); }
-};
-
 // unique.hip: sorted distinct symbols on the device (hipcub radix sort + unique); *n_uniq on the host
 int device_unique_u64(const uint64_t *d_sym, uint64_t total, uint64_t *d_uniq, uint64_t cap, uint64_t *n_uniq,
                       hipStream_t st);
 // unique.hip, for delivery.hip: the per-context table of the signature's rank keys (sig_dev.h; RANK_KEYS entries,
 // built on first use), and the equality classes of d_sig[2 * N]: first[i] = the smallest j with sig_j == sig_i
-// (radix sort with the index as payload; scratch ctx->buf[6]). The caller holds ctx.
+// (radix sort with the index as payload; scratch SLOT_CLASSES). The caller holds ctx.
 int sig_rank_keys(nmz_ctx *ctx, const ulonglong2 **out);
 int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_first, hipStream_t st);
 
 // match.hip, for contrast.hip (nmz_order_contrast_runs). match_validate: every limit of the host forms, no device.
 int match_validate(const uint64_t *sym, const int64_t *arrival, uint32_t E, const uint64_t *run_off,
                    const uint64_t *run_sym, uint64_t n_runs);
-// One host-form match on the context's stream; the caller holds ctx and has validated. run() builds the universe's
-// plan, takes rows, offsets and symbols from the context's pool for the call, uploads the CSR and enqueues the
-// match: *d_pos = the [n_runs][E] rows. The destructor drains the stream before plan and buffer go back.
-struct MatchCall {
-    nmz_ctx *ctx;
-    nmz_match_plan *plan = nullptr;
-    DevBuf work;
-    explicit MatchCall(nmz_ctx *c) : ctx(c) { work.pool = &c->pool; }
-    ~MatchCall();
-    int run(const uint64_t *sym, const int64_t *arrival, uint32_t E, const uint64_t *run_off,
-            const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos);
-};
+// One host-form match on the context's stream; the caller holds ctx and has validated. Builds the universe's plan
+// (the call owns it), takes rows, offsets and symbols from the context's pool as call.work, uploads the CSR and
+// enqueues the match: *d_pos = the [n_runs][E] rows.
+int match_call(nmz_ctx *ctx, HostCall &call, const uint64_t *sym, const int64_t *arrival, uint32_t E,
+               const uint64_t *run_off, const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos);
 
 // ed_align.hip, for ed_moves.hip (nmz_move_profile, nmz_ed_diff_profile). align_validate: every limit of
 // nmz_ed_align_pairs, no device; *max_len = the longest trace of the pairs. align_shape: the plan's shape for
@@ -61,14 +40,5 @@ int align_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint
 void align_plan_destroy_locked(nmz_ed_align_plan *p);
 int align_enqueue(nmz_ed_align_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
                   const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops);
-// One host-form call on the context's stream; the caller holds ctx and has validated. The destructor drains the
-// stream before plan and buffers go back to the pool.
-struct AlignCall {
-    nmz_ctx *ctx;
-    nmz_ed_align_plan *plan = nullptr;
-    DevBuf work;
-    explicit AlignCall(nmz_ctx *c) : ctx(c) { work.pool = &c->pool; }
-    ~AlignCall();
-};
 
 }  // namespace nmz

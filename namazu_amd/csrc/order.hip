@@ -195,17 +195,13 @@ static int order_plan_create_locked(nmz_ctx *ctx, const uint32_t *hint_off, cons
     p->mu = order_mu(p->m);
     p->max_seeds = max_seeds;
     const size_t ns = max_seeds ? max_seeds : 1;
-    int rc = p->mem.ensure(Carve::bytes_for(table.size(), 8) + Carve::bytes_for(C, sizeof(OrderCons)) +
-                           Carve::bytes_for(ns, 8) + Carve::bytes_for(bucket_hist_u32(ns), 4));
+    ScratchLayout lay;
+    lay.add(&p->d_table, table.size()).add(&p->d_cons, C).add(&p->d_h0, ns).add(&p->d_rows, bucket_hist_u32(ns));
+    int rc = lay.bind(p->mem);
     if (rc != NMZ_OK) {
         delete p;
         return rc;
     }
-    Carve cv(p->mem.ptr);
-    p->d_table = cv.take<uint64_t>(table.size());
-    p->d_cons = cv.take<OrderCons>(C);
-    p->d_h0 = cv.take<uint64_t>(ns);
-    p->d_rows = cv.take<uint32_t>(bucket_hist_u32(ns));
     hipStream_t st = ctx->stream;
     hipError_t e = hipMemcpyAsync(p->d_table, table.data(), table.size() * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(p->d_cons, oc.data(), C * sizeof(OrderCons), hipMemcpyHostToDevice, st);
@@ -277,36 +273,28 @@ static int order_sweep_host(nmz_ctx *ctx, const uint32_t *seed_off, const uint8_
     NMZ_CHECK(k <= 256, "top-k supports k <= 256");
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
+    HostCall call(ctx);
     nmz_replayable_order_plan *plan = nullptr;
     NMZ_TRY(order_plan_create_locked(ctx, hint_off, hint_bytes, n_events, max_interval_ns, arrival_ns, constraints,
                                      n_constraints, n_seeds, &plan));
-    struct PlanGuard {
-        nmz_replayable_order_plan *p;
-        ~PlanGuard() { order_plan_destroy_locked(p); }
-    } pg{plan};
+    call.own_plan<order_plan_destroy_locked>(plan);
     hipStream_t st = ctx->stream;
     const uint32_t kk = topk ? k : 0;
-    const uint64_t sbytes = (!decimal && n_seeds) ? seed_off[n_seeds] : 0;
-    NMZ_CHECK(sbytes == 0 || seed_bytes, "seed_bytes is NULL");
-    NMZ_TRY(ctx->buf[0].ensure(Carve::bytes_for(n_seeds + 1, 4) + Carve::bytes_for(sbytes + 1, 1) +
-                               Carve::bytes_for(n_seeds + 1, sizeof(nmz_order_stats)) +
-                               Carve::bytes_for(kk + 1, sizeof(nmz_topk_entry))));
-    Carve cv(ctx->buf[0].ptr);
-    uint32_t *d_soff = cv.take<uint32_t>(n_seeds + 1);
-    uint8_t *d_sb = cv.take<uint8_t>(sbytes + 1);
-    nmz_order_stats *d_stats = cv.take<nmz_order_stats>(n_seeds + 1);
-    nmz_topk_entry *d_tk = cv.take<nmz_topk_entry>(kk + 1);
-    if (!decimal && n_seeds) {
-        NMZ_HIP(hipMemcpyAsync(d_soff, seed_off, (n_seeds + 1) * 4, hipMemcpyHostToDevice, st));
-        if (sbytes) NMZ_HIP(hipMemcpyAsync(d_sb, seed_bytes, sbytes, hipMemcpyHostToDevice, st));
-    }
+    uint64_t sbytes;
+    NMZ_TRY(seed_csr_bytes(seed_off, seed_bytes, n_seeds, decimal, &sbytes));
+    uint32_t *d_soff;
+    uint8_t *d_sb;
+    nmz_order_stats *d_stats;
+    nmz_topk_entry *d_tk;
+    ScratchLayout lay;
+    lay.add(&d_soff, n_seeds + 1).add(&d_sb, sbytes + 1).add(&d_stats, n_seeds + 1).add(&d_tk, kk + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_SWEEP_HOST]));
+    NMZ_TRY(upload_seeds(d_soff, d_sb, seed_off, seed_bytes, n_seeds, decimal, st));
     NMZ_TRY(order_run(plan, st, decimal ? nullptr : d_soff, d_sb, seed_lo, n_seeds, decimal ? seed_lo : 0, kk,
                       stats ? d_stats : nullptr, d_tk));
-    if (stats && n_seeds)
-        NMZ_HIP(hipMemcpyAsync(stats, d_stats, n_seeds * sizeof(nmz_order_stats), hipMemcpyDeviceToHost, st));
-    if (kk) NMZ_HIP(hipMemcpyAsync(topk, d_tk, kk * sizeof(nmz_topk_entry), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (stats) NMZ_TRY(copy_d2h(stats, d_stats, n_seeds, st));
+    NMZ_TRY(copy_d2h(topk, d_tk, kk, st));
+    return call.done();
 }
 
 }  // namespace nmz

@@ -438,37 +438,33 @@ static int ps_sweep_launch(nmz_random_plan *plan, hipStream_t st, uint64_t seed0
 
 // uploads the inputs of k_procset_decide and runs it for n_seeds seeds; the results stay on the device
 struct PsDecideBufs {
+    uint64_t *d_eh, *d_off;
+    uint8_t *d_ec;
+    uint4 *d_events;
     int64_t *d_del;
     nmz_proc_attr *d_attr;
     uint32_t *d_ovf;
-    uint4 *d_events;
 };
-static size_t ps_decide_bytes(uint32_t E, uint64_t n_seeds, uint64_t total) {
-    return Carve::bytes_for(E + 1, 8) * 2 + Carve::bytes_for(E + 1, 1) + Carve::bytes_for(E + 1, 16) +
-           Carve::bytes_for(n_seeds * E + 1, 8) + Carve::bytes_for(n_seeds * total + 1, 16) + Carve::bytes_for(4, 4);
+// the fields of the decisions of n_seeds seeds over E events with `total` processes, appended to the call's layout
+static void ps_decide_layout(ScratchLayout &lay, uint32_t E, uint64_t n_seeds, uint64_t total, PsDecideBufs &o) {
+    lay.add(&o.d_eh, E + 1).add(&o.d_off, E + 1).add(&o.d_ec, E + 1).add(&o.d_events, E + 1);
+    lay.add(&o.d_del, n_seeds * E + 1).add(&o.d_attr, n_seeds * total + 1).add(&o.d_ovf, 4);
 }
-static int ps_decide_launch(Carve &cv, hipStream_t st, uint64_t seed0, uint64_t n_seeds, const uint64_t *evhash,
-                            const uint8_t *evclass, const std::vector<PsEvent> &events,
-                            const std::vector<uint64_t> &off, const RandomKParams &kp, const nmz_procset_params &pp,
-                            PsDecideBufs &o) {
+static int ps_decide_launch(const PsDecideBufs &o, hipStream_t st, uint64_t seed0, uint64_t n_seeds,
+                            const uint64_t *evhash, const uint8_t *evclass, const std::vector<PsEvent> &events,
+                            const std::vector<uint64_t> &off, const RandomKParams &kp, const nmz_procset_params &pp) {
     const uint32_t E = (uint32_t)events.size();
     const uint64_t total = off[E];
-    uint64_t *d_eh = cv.take<uint64_t>(E + 1);
-    uint64_t *d_off = cv.take<uint64_t>(E + 1);
-    uint8_t *d_ec = cv.take<uint8_t>(E + 1);
-    o.d_events = cv.take<uint4>(E + 1);
-    o.d_del = cv.take<int64_t>(n_seeds * E + 1);
-    o.d_attr = cv.take<nmz_proc_attr>(n_seeds * total + 1);
-    o.d_ovf = cv.take<uint32_t>(4);
     NMZ_HIP(hipMemsetAsync(o.d_ovf, 0, 4, st));
+    NMZ_TRY(copy_h2d(o.d_eh, evhash, E, st));
+    NMZ_TRY(copy_h2d(o.d_off, off.data(), E, st));
+    NMZ_TRY(copy_h2d(o.d_ec, evclass, E, st));
     if (E == 0) return NMZ_OK;
-    NMZ_HIP(hipMemcpyAsync(d_eh, evhash, (size_t)E * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)E * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_ec, evclass, E, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(o.d_events, events.data(), (size_t)E * 16, hipMemcpyHostToDevice, st));
+    // a PsEvent is loaded as one uint4
+    NMZ_HIP(hipMemcpyAsync(o.d_events, events.data(), (size_t)E * sizeof(PsEvent), hipMemcpyHostToDevice, st));
     if (n_seeds) {
-        hipLaunchKernelGGL(k_procset_decide, dim3(ceil_div(n_seeds * E, 256)), dim3(256), 0, st, seed0, n_seeds, d_eh,
-                           d_ec, o.d_events, d_off, total, E, kp, pp, o.d_del, o.d_attr, o.d_ovf);
+        hipLaunchKernelGGL(k_procset_decide, dim3(ceil_div(n_seeds * E, 256)), dim3(256), 0, st, seed0, n_seeds,
+                           o.d_eh, o.d_ec, o.d_events, o.d_off, total, E, kp, pp, o.d_del, o.d_attr, o.d_ovf);
         NMZ_HIP(hipGetLastError());
     }
     return NMZ_OK;
@@ -550,15 +546,17 @@ int nmz_procset_decide(nmz_ctx *ctx, uint64_t seed, const uint64_t *evhash, cons
     const uint64_t total = off[n_events];
     NMZ_CHECK(evhash && delays && (attrs || total == 0), "NULL argument");
     hipStream_t st = ctx->stream;
-    NMZ_TRY(ctx->buf[9].ensure(ps_decide_bytes(n_events, 1, total)));
-    Carve cv(ctx->buf[9].ptr);
-    PsDecideBufs d;
-    NMZ_TRY(ps_decide_launch(cv, st, seed, 1, evhash, evclass, events, off, kp, *procset_params, d));
     uint32_t ovf = 0;
-    NMZ_HIP(hipMemcpyAsync(delays, d.d_del, (uint64_t)n_events * 8, hipMemcpyDeviceToHost, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(attrs, d.d_attr, total * sizeof(nmz_proc_attr), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(&ovf, d.d_ovf, 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
+    HostCall call(ctx);
+    PsDecideBufs d;
+    ScratchLayout lay;
+    ps_decide_layout(lay, n_events, 1, total, d);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_RANDOM_PROCSET_DECIDE]));
+    NMZ_TRY(ps_decide_launch(d, st, seed, 1, evhash, evclass, events, off, kp, *procset_params));
+    NMZ_TRY(copy_d2h(delays, d.d_del, n_events, st));
+    NMZ_TRY(copy_d2h(attrs, d.d_attr, total, st));
+    NMZ_TRY(copy_d2h(&ovf, d.d_ovf, 1, st));
+    NMZ_TRY(call.done());
     if (ovf) return fail(NMZ_ERANGE, "a decision needed more than 607 Go rng outputs");
     return NMZ_OK;
 }
@@ -579,27 +577,24 @@ int nmz_procset_sweep(nmz_ctx *ctx, uint64_t seed0, uint64_t n_seeds, const uint
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     hipStream_t st = ctx->stream;
+    uint32_t ovf = 0;
+    HostCall call(ctx);
     nmz_random_plan *plan = nullptr;
     NMZ_TRY(random_plan_create(ctx, evhash, evclass, n_events, random_params, n_seeds, &plan));
-    struct PlanGuard {
-        nmz_random_plan *p;
-        ~PlanGuard() { random_plan_free(p); }
-    } pg{plan};
+    call.own_plan<random_plan_free>(plan);
     const uint64_t total = off[n_events];
     const uint64_t tk_entries = topk_scratch_entries(n_seeds, k);
-    const size_t need = Carve::bytes_for(n_seeds + 1, sizeof(nmz_procset_stats)) * 2 +
-                        ps_decide_bytes(n_events, n_dump_seeds, total) +
-                        Carve::bytes_for(tk_entries + k + 1, sizeof(nmz_topk_entry)) +
-                        Carve::bytes_for(k + 1, sizeof(nmz_procset_topk_entry));
-    NMZ_TRY(ctx->buf[1].ensure(need));
-    Carve cv(ctx->buf[1].ptr);
-    nmz_procset_stats *d_stats = cv.take<nmz_procset_stats>(n_seeds + 1);
-    nmz_sched_stats *d_keys = cv.take<nmz_sched_stats>(n_seeds + 1);
-    nmz_topk_entry *d_tk = cv.take<nmz_topk_entry>(tk_entries + k + 1);
-    nmz_procset_topk_entry *d_out = cv.take<nmz_procset_topk_entry>(k + 1);
-    // the events and, for the dump rows, every decision of the first n_dump_seeds seeds in full
+    nmz_procset_stats *d_stats;
+    nmz_sched_stats *d_keys;
+    nmz_topk_entry *d_tk;
+    nmz_procset_topk_entry *d_out;
     PsDecideBufs d;
-    NMZ_TRY(ps_decide_launch(cv, st, seed0, n_dump_seeds, evhash, evclass, events, off, plan->kp, *procset_params, d));
+    ScratchLayout lay;
+    lay.add(&d_stats, n_seeds + 1).add(&d_keys, n_seeds + 1).add(&d_tk, tk_entries + k + 1).add(&d_out, k + 1);
+    ps_decide_layout(lay, n_events, n_dump_seeds, total, d);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_RANDOM_PROCSET_SWEEP]));
+    // the events and, for the dump rows, every decision of the first n_dump_seeds seeds in full
+    NMZ_TRY(ps_decide_launch(d, st, seed0, n_dump_seeds, evhash, evclass, events, off, plan->kp, *procset_params));
     if (n_seeds) {
         if (n_events)
             NMZ_TRY(ps_sweep_launch(plan, st, seed0, n_seeds, d.d_events, *procset_params, d_stats, d.d_ovf));
@@ -614,18 +609,12 @@ int nmz_procset_sweep(nmz_ctx *ctx, uint64_t seed0, uint64_t n_seeds, const uint
         hipLaunchKernelGGL(k_procset_topk_out, dim3(1), dim3(256), 0, st, d_tk + tk_entries, k, descending, d_out);
         NMZ_HIP(hipGetLastError());
     }
-    uint32_t ovf = 0;
-    const uint64_t nd = n_dump_seeds * n_events;
-    if (stats && n_seeds)
-        NMZ_HIP(hipMemcpyAsync(stats, d_stats, n_seeds * sizeof(nmz_procset_stats), hipMemcpyDeviceToHost, st));
-    if (delays && nd) NMZ_HIP(hipMemcpyAsync(delays, d.d_del, nd * 8, hipMemcpyDeviceToHost, st));
-    if (attrs && n_dump_seeds * total)
-        NMZ_HIP(hipMemcpyAsync(attrs, d.d_attr, n_dump_seeds * total * sizeof(nmz_proc_attr), hipMemcpyDeviceToHost,
-                               st));
-    if (topk && k)
-        NMZ_HIP(hipMemcpyAsync(topk, d_out, k * sizeof(nmz_procset_topk_entry), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(&ovf, d.d_ovf, 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
+    if (stats) NMZ_TRY(copy_d2h(stats, d_stats, n_seeds, st));
+    if (delays) NMZ_TRY(copy_d2h(delays, d.d_del, n_dump_seeds * n_events, st));
+    if (attrs) NMZ_TRY(copy_d2h(attrs, d.d_attr, n_dump_seeds * total, st));
+    if (topk) NMZ_TRY(copy_d2h(topk, d_out, k, st));
+    NMZ_TRY(copy_d2h(&ovf, d.d_ovf, 1, st));
+    NMZ_TRY(call.done());
     if (ovf) return fail(NMZ_ERANGE, "a decision needed more than 607 Go rng outputs");
     return NMZ_OK;
 }

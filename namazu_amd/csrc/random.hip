@@ -383,22 +383,15 @@ static uint32_t random_ec(uint64_t S) {
     return env ? env : (S >= RANDOM_EC_LARGE_SEEDS ? RANDOM_EC_LARGE : RANDOM_EC);
 }
 
-static size_t random_seed_scratch_bytes(uint64_t S) {
-    return Carve::bytes_for(S, 8) * 2 + Carve::bytes_for(S, 4) + Carve::bytes_for(BUCKET_SMALL_U32, 4) +
-           Carve::bytes_for(bucket_hist_u32(S), 4) + Carve::bytes_for(S / 64 + 257, 16) + Carve::bytes_for(4, 4);
-}
-
-static Buckets carve_random(void *p, uint64_t S, uint64_t **h0, uint32_t **counter) {
-    Carve cv(p);
-    *h0 = cv.take<uint64_t>(S);
+// a plan's seed scratch for S seeds: the prefix states, the buckets, the sweep's work-item counter
+struct RandomSeedScratch {
+    uint64_t *h0;
     Buckets b;
-    b.sorted_h0 = cv.take<uint64_t>(S);
-    b.sorted_idx = cv.take<uint32_t>(S);
-    buckets_small(cv.take<uint32_t>(BUCKET_SMALL_U32), b);
-    b.hist = cv.take<uint32_t>(bucket_hist_u32(S));
-    b.units = cv.take<uint4>(S / 64 + 257);
-    *counter = cv.take<uint32_t>(4);
-    return b;
+    uint32_t *small, *counter;
+};
+static void random_seed_layout(ScratchLayout &lay, uint64_t S, RandomSeedScratch &s) {
+    lay.add(&s.h0, S).add(&s.b.sorted_h0, S).add(&s.b.sorted_idx, S).add(&s.small, BUCKET_SMALL_U32);
+    lay.add(&s.b.hist, bucket_hist_u32(S)).add(&s.b.units, S / 64 + 257).add(&s.counter, 4);
 }
 
 int random_plan_create(nmz_ctx *ctx, const uint64_t *evhash, const uint8_t *evclass, uint32_t E,
@@ -423,17 +416,17 @@ int random_plan_create(nmz_ctx *ctx, const uint64_t *evhash, const uint8_t *evcl
         delete p;
         return code;
     };
-    int rc = p->table_mem.ensure(Carve::bytes_for((size_t)256 * E + 1, 16) + Carve::bytes_for(E + 1, 8) +
-                                 Carve::bytes_for(E + 1, 1));
-    if (rc == NMZ_OK) rc = p->seed_scratch.ensure(random_seed_scratch_bytes(max_seeds));
+    uint64_t *d_eh;
+    uint8_t *d_ec;
+    ScratchLayout lay, seed_lay;
+    RandomSeedScratch ss;
+    lay.add(&p->d_table, (size_t)256 * E + 1).add(&d_eh, E + 1).add(&d_ec, E + 1);
+    random_seed_layout(seed_lay, max_seeds, ss);
+    int rc = lay.bind(p->table_mem);
+    if (rc == NMZ_OK) rc = seed_lay.bind(p->seed_scratch);
     if (rc != NMZ_OK) return cleanup(rc);
-    Carve cv(p->table_mem.ptr);
-    p->d_table = cv.take<uint4>((size_t)256 * E + 1);
-    uint64_t *d_eh = cv.take<uint64_t>(E + 1);
-    uint8_t *d_ec = cv.take<uint8_t>(E + 1);
     if (E) {
-        if (hipMemcpyAsync(d_eh, evhash, (size_t)E * 8, hipMemcpyHostToDevice, st) ||
-            hipMemcpyAsync(d_ec, evclass, E, hipMemcpyHostToDevice, st))
+        if (copy_h2d(d_eh, evhash, E, st) != NMZ_OK || copy_h2d(d_ec, evclass, E, st) != NMZ_OK)
             return cleanup(fail(NMZ_EHIP, "plan upload failed"));
         hipLaunchKernelGGL(k_random_table, dim3(E), dim3(256), 0, st, d_eh, d_ec, E, p->d_table);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
@@ -452,10 +445,15 @@ void random_plan_free(nmz_random_plan *p) {
 
 int random_bucket(nmz_random_plan *p, hipStream_t st, uint64_t seed0, uint64_t S, Buckets &b, uint32_t **counter) {
     NMZ_CHECK(S <= p->max_seeds, "more seeds than the plan was created for");
-    uint64_t *d_h0;
-    b = carve_random(p->seed_scratch.ptr, p->max_seeds, &d_h0, counter);
-    hipLaunchKernelGGL(k_random_prefix, dim3(ceil_div(S, BUCKET_BLK)), dim3(256), 0, st, seed0, S, d_h0, b.hist);
-    return bucket_seeds_counted(st, d_h0, S, 64, b, *counter);
+    ScratchLayout lay;
+    RandomSeedScratch ss;
+    random_seed_layout(lay, p->max_seeds, ss);
+    NMZ_TRY(lay.place(p->seed_scratch.ptr));  // sized by random_plan_create
+    buckets_small(ss.small, ss.b);
+    b = ss.b;
+    *counter = ss.counter;
+    hipLaunchKernelGGL(k_random_prefix, dim3(ceil_div(S, BUCKET_BLK)), dim3(256), 0, st, seed0, S, ss.h0, b.hist);
+    return bucket_seeds_counted(st, ss.h0, S, 64, b, *counter);
 }
 
 static int random_run(nmz_random_plan *p, hipStream_t st, uint64_t seed0, uint64_t S, nmz_sched_stats *d_stats) {
@@ -470,8 +468,8 @@ static int random_run(nmz_random_plan *p, hipStream_t st, uint64_t seed0, uint64
     const uint64_t stride = (p->max_seeds / 64 + 257) * 64;
     nmz_sched_stats *part = nullptr;
     if (n_chunks > 1) {
-        NMZ_TRY(p->partial.ensure(Carve::bytes_for(stride * n_chunks, sizeof(nmz_sched_stats))));
-        part = p->partial.as<nmz_sched_stats>();
+        ScratchLayout lay;
+        NMZ_TRY(lay.add(&part, stride * n_chunks).bind(p->partial));
     }
     const unsigned grid = (unsigned)std::min<uint64_t>(p->ctx->n_cu * 8ull, ceil_div(max_units * n_chunks, 4));
     {
@@ -535,28 +533,22 @@ int nmz_random_sweep(nmz_ctx *ctx, uint64_t seed0, uint64_t n_seeds, const uint6
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     hipStream_t st = ctx->stream;
+    uint32_t ovf = 0;
+    HostCall call(ctx);
     nmz_random_plan *plan = nullptr;
     NMZ_TRY(random_plan_create(ctx, evhash, evclass, n_events, params, n_seeds, &plan));
-    struct PlanGuard {
-        nmz_random_plan *p;
-        ~PlanGuard() {
-            p->table_mem.release();
-            p->seed_scratch.release();
-            p->partial.release();
-            delete p;
-        }
-    } pg{plan};
+    call.own_plan<random_plan_free>(plan);
     const uint64_t nd = n_dump_seeds * n_events;
     const uint64_t tk_entries = topk_scratch_entries(n_seeds, k);
-    size_t need = Carve::bytes_for(n_seeds + 1, sizeof(nmz_sched_stats)) + Carve::bytes_for(nd + 1, 8) +
-                  Carve::bytes_for(nd + 1, 1) + Carve::bytes_for(4, 4) + Carve::bytes_for(tk_entries + k + 1, 24);
-    NMZ_TRY(ctx->buf[1].ensure(need));
-    Carve cv(ctx->buf[1].ptr);
-    nmz_sched_stats *d_stats = cv.take<nmz_sched_stats>(n_seeds + 1);
-    int64_t *d_del = cv.take<int64_t>(nd + 1);
-    uint8_t *d_flt = cv.take<uint8_t>(nd + 1);
-    uint32_t *d_ovf = cv.take<uint32_t>(4);
-    nmz_topk_entry *d_tk = cv.take<nmz_topk_entry>(tk_entries + k + 1);
+    nmz_sched_stats *d_stats;
+    int64_t *d_del;
+    uint8_t *d_flt;
+    uint32_t *d_ovf;
+    nmz_topk_entry *d_tk;
+    ScratchLayout lay;
+    lay.add(&d_stats, n_seeds + 1).add(&d_del, nd + 1).add(&d_flt, nd + 1).add(&d_ovf, 4);
+    lay.add(&d_tk, tk_entries + k + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_RANDOM_PROCSET_SWEEP]));
     NMZ_HIP(hipMemsetAsync(d_ovf, 0, 4, st));
     if (n_events == 0) {
         for (uint64_t i = 0; i < n_seeds && stats; ++i) stats_empty(stats[i]);
@@ -568,15 +560,12 @@ int nmz_random_sweep(nmz_ctx *ctx, uint64_t seed0, uint64_t n_seeds, const uint6
         NMZ_HIP(hipGetLastError());
     }
     if (k && n_events) NMZ_TRY(topk_select(st, d_stats, n_seeds, seed0, k, d_tk, d_tk + tk_entries));
-    uint32_t ovf = 0;
-    if (stats && n_seeds && n_events)
-        NMZ_HIP(hipMemcpyAsync(stats, d_stats, n_seeds * sizeof(nmz_sched_stats), hipMemcpyDeviceToHost, st));
-    if (delays && nd) NMZ_HIP(hipMemcpyAsync(delays, d_del, nd * 8, hipMemcpyDeviceToHost, st));
-    if (faults && nd) NMZ_HIP(hipMemcpyAsync(faults, d_flt, nd, hipMemcpyDeviceToHost, st));
-    if (topk && k && n_events)
-        NMZ_HIP(hipMemcpyAsync(topk, d_tk + tk_entries, k * sizeof(nmz_topk_entry), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
+    if (stats && n_events) NMZ_TRY(copy_d2h(stats, d_stats, n_seeds, st));
+    if (delays) NMZ_TRY(copy_d2h(delays, d_del, nd, st));
+    if (faults) NMZ_TRY(copy_d2h(faults, d_flt, nd, st));
+    if (topk && n_events) NMZ_TRY(copy_d2h(topk, d_tk + tk_entries, k, st));
+    NMZ_TRY(copy_d2h(&ovf, d_ovf, 1, st));
+    NMZ_TRY(call.done());
     if (ovf) return fail(NMZ_ERANGE, "a decision needed more than 607 Go rng outputs");
     if (topk && k && n_events == 0) {
         // no events: every seed ties at (0 faults, sum 0) -> smallest seeds first
@@ -637,25 +626,25 @@ int nmz_random_decide(nmz_ctx *ctx, uint64_t seed, const uint64_t *evhash, const
         NMZ_CHECK((evclass[e] & ~(NMZ_EV_PRIORITIZED | NMZ_EV_FAULTABLE)) == 0,
                   "evclass has unknown bits (ProcSetEvent decisions: nmz_procset_decide[_host], nmz_procset_sweep)");
     hipStream_t st = ctx->stream;
-    NMZ_TRY(ctx->buf[9].ensure(Carve::bytes_for(n_events, 8) * 2 + Carve::bytes_for(n_events, 1) * 2 +
-                               Carve::bytes_for(4, 4)));
-    Carve cv(ctx->buf[9].ptr);
-    uint64_t *d_eh = cv.take<uint64_t>(n_events);
-    int64_t *d_del = cv.take<int64_t>(n_events);
-    uint8_t *d_ec = cv.take<uint8_t>(n_events);
-    uint8_t *d_flt = cv.take<uint8_t>(n_events);
-    uint32_t *d_ovf = cv.take<uint32_t>(4);
+    uint32_t ovf = 0;
+    HostCall call(ctx);
+    uint64_t *d_eh;
+    int64_t *d_del;
+    uint8_t *d_ec, *d_flt;
+    uint32_t *d_ovf;
+    ScratchLayout lay;
+    lay.add(&d_eh, n_events).add(&d_del, n_events).add(&d_ec, n_events).add(&d_flt, n_events).add(&d_ovf, 4);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_RANDOM_PROCSET_DECIDE]));
     NMZ_HIP(hipMemsetAsync(d_ovf, 0, 4, st));
-    NMZ_HIP(hipMemcpyAsync(d_eh, evhash, (uint64_t)n_events * 8, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_ec, evclass, n_events, hipMemcpyHostToDevice, st));
+    NMZ_TRY(copy_h2d(d_eh, evhash, n_events, st));
+    NMZ_TRY(copy_h2d(d_ec, evclass, n_events, st));
     hipLaunchKernelGGL(k_random_decide, dim3(ceil_div(n_events, 256)), dim3(256), 0, st, seed, d_eh, d_ec, n_events,
                        kp, d_del, d_flt, d_ovf);
     NMZ_HIP(hipGetLastError());
-    uint32_t ovf = 0;
-    NMZ_HIP(hipMemcpyAsync(delays, d_del, (uint64_t)n_events * 8, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(faults, d_flt, n_events, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
+    NMZ_TRY(copy_d2h(delays, d_del, n_events, st));
+    NMZ_TRY(copy_d2h(faults, d_flt, n_events, st));
+    NMZ_TRY(copy_d2h(&ovf, d_ovf, 1, st));
+    NMZ_TRY(call.done());
     if (ovf) return fail(NMZ_ERANGE, "a decision needed more than 607 Go rng outputs");
     return NMZ_OK;
 }

@@ -425,16 +425,21 @@ static int plan_create(nmz_ctx *ctx, const uint32_t *hint_off, const uint8_t *hi
     std::vector<WtClass> woc;
     const bool fused = E && !(ab_env("NMZ_WT_FUSED") && atoi(ab_env("NMZ_WT_FUSED")) == 0) &&
                        wt_layout(p->wt, ctx, E, cls.data(), (uint32_t)cls.size(), p->mod, true, woc);
-    size_t need = Carve::bytes_for(cls.size() + 1, sizeof(ClassInfo)) + Carve::bytes_for((size_t)256 * E + 1, 16) +
-                  Carve::bytes_for(E + 1, 4) * 2 + Carve::bytes_for(nbytes + 1, 1);
-    if (fused) need += Carve::bytes_for(woc.size(), sizeof(WtClass)) + Carve::bytes_for(256, 8);
-    int rc = p->plan_mem.ensure(need);
+    // the small inputs first (one contiguous region, packed in the context's pinned staging at the same offsets:
+    // one asynchronous upload), then the table
+    uint32_t *d_perm;
+    WtClass *d_wcls = nullptr;
+    unsigned long long *d_rowsum = nullptr;
+    ScratchLayout lay;
+    lay.add(&p->d_classes, cls.size() + 1).add(&d_perm, E + 1).add(&p->d_hoff, E + 1).add(&p->d_hbytes, nbytes + 1);
+    if (fused) lay.add(&d_wcls, woc.size()).add(&d_rowsum, 256);
+    lay.add(&p->d_table, (size_t)256 * E + 1);
+    int rc = lay.bind(p->plan_mem);
     SeedScratch sc0{};
     const bool seeds = E && p->mod.kind != MOD_ZERO;
     if (rc == NMZ_OK && seeds) {
-        rc = p->seed_scratch.ensure(seed_scratch_bytes(max_seeds));
+        rc = seed_scratch_bind(p->seed_scratch, max_seeds, sc0);
         if (rc == NMZ_OK) {  // the work-item counter starts at zero (k_bucket_scatter re-zeroes it)
-            sc0 = carve_seed_scratch(p->seed_scratch.ptr, max_seeds);
             if (!fused && hipMemsetAsync(sc0.counter, 0, 4 * sizeof(uint32_t), st) != hipSuccess)
                 rc = fail(NMZ_EHIP, "hipMemsetAsync of the seed scratch failed");
         }
@@ -445,17 +450,9 @@ static int plan_create(nmz_ctx *ctx, const uint32_t *hint_off, const uint8_t *hi
         return code;
     };
     if (rc != NMZ_OK) return cleanup(rc);
-    // the small inputs first (one contiguous region, packed in the context's pinned staging at the same offsets:
-    // one asynchronous upload), then the table
-    Carve cv(p->plan_mem.ptr);
-    p->d_classes = cv.take<ClassInfo>(cls.size() + 1);
-    uint32_t *d_perm = cv.take<uint32_t>(E + 1);
-    uint32_t *d_hoff = p->d_hoff = cv.take<uint32_t>(E + 1);
-    uint8_t *d_hbytes = p->d_hbytes = cv.take<uint8_t>(nbytes + 1);
-    WtClass *d_wcls = fused ? cv.take<WtClass>(woc.size()) : nullptr;
-    unsigned long long *d_rowsum = fused ? cv.take<unsigned long long>(256) : nullptr;
-    const size_t in_bytes = (size_t)(reinterpret_cast<char *>(cv.take<uint4>(0)) - reinterpret_cast<char *>(p->plan_mem.ptr));
-    p->d_table = cv.take<uint4>((size_t)256 * E + 1);
+    uint32_t *d_hoff = p->d_hoff;
+    uint8_t *d_hbytes = p->d_hbytes;
+    const size_t in_bytes = (size_t)(reinterpret_cast<char *>(p->d_table) - static_cast<char *>(p->plan_mem.ptr));
     if (E) {
         HostPin &pin = ctx->pin[0];
         if (pin.ensure(in_bytes) != NMZ_OK) return cleanup(NMZ_ENOMEM);
@@ -482,27 +479,29 @@ static int plan_create(nmz_ctx *ctx, const uint32_t *hint_off, const uint8_t *hi
         if (!p->wt.on) {
             // unsorted table into scratch (the context's, grow-only: no free, so no device sync), then the
             // per-(L, class) C sort into place
-            DevBuf &tmp = ctx->buf[10];
-            if (tmp.ensure((size_t)256 * E * sizeof(uint4)) != NMZ_OK) return cleanup(NMZ_ENOMEM);
+            uint4 *d_tmp;
+            ScratchLayout tmp_lay;
+            const int trc = tmp_lay.add(&d_tmp, (size_t)256 * E).bind(ctx->buf[SLOT_PLAN_TMP]);
+            if (trc != NMZ_OK) return cleanup(trc);
             hipLaunchKernelGGL(k_replayable_table, dim3(E), dim3(256), 0, st, d_hoff, d_hbytes, d_perm, E, p->mod.m,
-                               p->mod.m32ok ? 1 : 0, tmp.as<uint4>());
+                               p->mod.m32ok ? 1 : 0, d_tmp);
             uint32_t max_class = 0;
             for (const ClassInfo &c : cls) max_class = std::max(max_class, c.count);
             bool bad = false;
             if (max_class <= SEG_SORT_MAX) {  // LDS sort per segment
                 hipLaunchKernelGGL(k_replayable_table_segsort, dim3(p->n_classes, 256), dim3(1024), 0, st,
-                                   tmp.as<uint4>(), p->d_classes, E, p->d_table);
+                                   d_tmp, p->d_classes, E, p->d_table);
                 // no sync when the order-query images follow: oq_build synchronises after its kernels
                 bad = hipGetLastError() != hipSuccess ||
                       (!p->mod.m32ok && hipStreamSynchronize(st) != hipSuccess);
             } else if (max_class <= 16384) {  // O(n^2) rank sort on the device
                 hipLaunchKernelGGL(k_replayable_table_sort, dim3(ceil_div(E, 256), 256), dim3(256), 0, st,
-                                   tmp.as<uint4>(), p->d_classes, p->n_classes, E, p->d_table);
+                                   d_tmp, p->d_classes, p->n_classes, E, p->d_table);
                 bad = hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess;
             } else {  // very large classes: sort the segments on the host
                 std::vector<uint4> h((size_t)256 * E);
                 bad = hipGetLastError() != hipSuccess ||
-                      hipMemcpyAsync(h.data(), tmp.ptr, h.size() * sizeof(uint4), hipMemcpyDeviceToHost, st) !=
+                      hipMemcpyAsync(h.data(), d_tmp, h.size() * sizeof(uint4), hipMemcpyDeviceToHost, st) !=
                           hipSuccess ||
                       hipStreamSynchronize(st) != hipSuccess;
                 if (!bad) {
@@ -625,12 +624,12 @@ int nmz_replayable_sweep_traces(nmz_ctx *ctx, uint32_t n_traces, const uint32_t 
     for (int i = 0; i < 3; ++i)
         if (!ctx->sweep_ev[i]) NMZ_HIP(hipEventCreateWithFlags(&ctx->sweep_ev[i], hipEventDisableTiming));
     const uint64_t S = n_seeds;
-    const size_t st_bytes = Carve::bytes_for(S, sizeof(nmz_sched_stats)), tk_bytes = Carve::bytes_for(k, sizeof(nmz_topk_entry));
-    NMZ_TRY(ctx->buf[11].ensure(2 * (st_bytes + tk_bytes)));
+    nmz_sched_stats *d_st[2];
+    nmz_topk_entry *d_tk[2];
+    ScratchLayout lay;
+    lay.add(&d_st[0], S).add(&d_st[1], S).add(&d_tk[0], k).add(&d_tk[1], k);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_KNN_LISTS_OR_TRACE_RINGS]));
     NMZ_TRY(ctx->tkpin.ensure(3 * (size_t)k * sizeof(nmz_topk_entry)));
-    Carve cv(ctx->buf[11].ptr);
-    nmz_sched_stats *d_st[2] = {cv.take<nmz_sched_stats>(S), cv.take<nmz_sched_stats>(S)};
-    nmz_topk_entry *d_tk[2] = {cv.take<nmz_topk_entry>(k), cv.take<nmz_topk_entry>(k)};
     nmz_topk_entry *h_tk = static_cast<nmz_topk_entry *>(ctx->tkpin.ptr);
     nmz_replayable_seeds *ss = nullptr;
     NMZ_TRY(seeds_create_locked(ctx, nullptr, nullptr, S, seed_lo, &ss));
@@ -710,29 +709,23 @@ int nmz_replayable_sweep(nmz_ctx *ctx, const uint32_t *seed_off, const uint8_t *
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     hipStream_t st = ctx->stream;
+    HostCall call(ctx);
     nmz_replayable_plan *plan = nullptr;
     NMZ_TRY(plan_create(ctx, hint_off, hint_bytes, n_events, max_interval_ns, n_seeds, &plan));
-    struct PlanGuard {
-        nmz_replayable_plan *p;
-        ~PlanGuard() { plan_destroy_locked(p); }
-    } pg{plan};
+    call.own_plan<plan_destroy_locked>(plan);
 
     const uint64_t sbytes = n_seeds ? seed_off[n_seeds] : 0;
     const uint64_t tk_entries = topk_scratch_entries(n_seeds, k);
-    size_t need = Carve::bytes_for(n_seeds + 1, 4) + Carve::bytes_for(sbytes + 1, 1) +
-                  Carve::bytes_for(n_seeds + 1, sizeof(nmz_sched_stats)) +
-                  Carve::bytes_for(n_dump_seeds * n_events + 1, 8) + Carve::bytes_for(tk_entries + k + 1, 24);
-    NMZ_TRY(ctx->buf[0].ensure(need));
-    Carve cv(ctx->buf[0].ptr);
-    uint32_t *d_soff = cv.take<uint32_t>(n_seeds + 1);
-    uint8_t *d_sb = cv.take<uint8_t>(sbytes + 1);
-    nmz_sched_stats *d_stats = cv.take<nmz_sched_stats>(n_seeds + 1);
-    int64_t *d_dump = cv.take<int64_t>(n_dump_seeds * n_events + 1);
-    nmz_topk_entry *d_tk = cv.take<nmz_topk_entry>(tk_entries + k + 1);
-    if (n_seeds) {
-        NMZ_HIP(hipMemcpyAsync(d_soff, seed_off, (n_seeds + 1) * 4, hipMemcpyHostToDevice, st));
-        if (sbytes) NMZ_HIP(hipMemcpyAsync(d_sb, seed_bytes, sbytes, hipMemcpyHostToDevice, st));
-    }
+    uint32_t *d_soff;
+    uint8_t *d_sb;
+    nmz_sched_stats *d_stats;
+    int64_t *d_dump;
+    nmz_topk_entry *d_tk;
+    ScratchLayout lay;
+    lay.add(&d_soff, n_seeds + 1).add(&d_sb, sbytes + 1).add(&d_stats, n_seeds + 1);
+    lay.add(&d_dump, n_dump_seeds * n_events + 1).add(&d_tk, tk_entries + k + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_SWEEP_HOST]));
+    NMZ_TRY(upload_seeds(d_soff, d_sb, seed_off, seed_bytes, n_seeds, false, st));
     NMZ_TRY(replayable_run(plan, st, d_soff, d_sb, n_seeds, d_stats));
     if (n_dump_seeds && n_events) {
         hipLaunchKernelGGL(k_replayable_dump, dim3(ceil_div(n_dump_seeds * n_events, 256)), dim3(256), 0, st, d_soff,
@@ -740,13 +733,10 @@ int nmz_replayable_sweep(nmz_ctx *ctx, const uint32_t *seed_off, const uint8_t *
         NMZ_HIP(hipGetLastError());
     }
     if (k) NMZ_TRY(topk_select(st, d_stats, n_seeds, 0, k, d_tk, d_tk + tk_entries));
-    if (stats && n_seeds)
-        NMZ_HIP(hipMemcpyAsync(stats, d_stats, n_seeds * sizeof(nmz_sched_stats), hipMemcpyDeviceToHost, st));
-    if (delays && n_dump_seeds && n_events)
-        NMZ_HIP(hipMemcpyAsync(delays, d_dump, n_dump_seeds * n_events * 8, hipMemcpyDeviceToHost, st));
-    if (topk && k) NMZ_HIP(hipMemcpyAsync(topk, d_tk + tk_entries, k * sizeof(nmz_topk_entry), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (stats) NMZ_TRY(copy_d2h(stats, d_stats, n_seeds, st));
+    if (delays) NMZ_TRY(copy_d2h(delays, d_dump, n_dump_seeds * n_events, st));
+    if (topk) NMZ_TRY(copy_d2h(topk, d_tk + tk_entries, k, st));
+    return call.done();
 }
 
 // Online decisions on the calling host thread (Replayable.QueueEvent decides at enqueue, replayablepolicy.go:
@@ -791,26 +781,26 @@ int nmz_replayable_decide(nmz_ctx *ctx, const uint8_t *seed, uint32_t seed_len, 
     const uint32_t hbytes = hint_off[n_events];
     NMZ_CHECK(hbytes == 0 || hint_bytes, "hint_bytes is NULL");
     hipStream_t st = ctx->stream;
-    NMZ_TRY(ctx->buf[8].ensure(Carve::bytes_for(2, 4) + Carve::bytes_for(seed_len + 1, 1) +
-                               Carve::bytes_for(n_events + 1, 4) + Carve::bytes_for(hbytes + 1, 1) +
-                               Carve::bytes_for(n_events, 8) + 256));
-    Carve cv(ctx->buf[8].ptr);
-    uint32_t *d_soff = cv.take<uint32_t>(2);
-    uint8_t *d_sb = cv.take<uint8_t>(seed_len + 1);
-    uint32_t *d_hoff = cv.take<uint32_t>(n_events + 1);
-    uint8_t *d_hb = cv.take<uint8_t>(hbytes + 1);
-    int64_t *d_out = cv.take<int64_t>(n_events);
     const uint32_t soff[2] = {0, seed_len};
-    NMZ_HIP(hipMemcpyAsync(d_soff, soff, 8, hipMemcpyHostToDevice, st));
-    if (seed_len) NMZ_HIP(hipMemcpyAsync(d_sb, seed, seed_len, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_hoff, hint_off, (n_events + 1) * 4, hipMemcpyHostToDevice, st));
-    if (hbytes) NMZ_HIP(hipMemcpyAsync(d_hb, hint_bytes, hbytes, hipMemcpyHostToDevice, st));
+    HostCall call(ctx);
+    uint32_t *d_soff, *d_hoff;
+    // d_spare: the 256 bytes the old size arithmetic added at the end, kept so that the slot's size is unchanged;
+    // it can go once sizes may change
+    uint8_t *d_sb, *d_hb, *d_spare;
+    int64_t *d_out;
+    ScratchLayout lay;
+    lay.add(&d_soff, 2).add(&d_sb, seed_len + 1).add(&d_hoff, n_events + 1).add(&d_hb, hbytes + 1);
+    lay.add(&d_out, n_events).add(&d_spare, 256);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_REPLAYABLE_DECIDE]));
+    NMZ_TRY(copy_h2d(d_soff, soff, 2, st));
+    NMZ_TRY(copy_h2d(d_sb, seed, seed_len, st));
+    NMZ_TRY(copy_h2d(d_hoff, hint_off, (size_t)n_events + 1, st));
+    NMZ_TRY(copy_h2d(d_hb, hint_bytes, hbytes, st));
     hipLaunchKernelGGL(k_replayable_dump, dim3(ceil_div(n_events, 256)), dim3(256), 0, st, d_soff, d_sb, (uint64_t)1,
                        d_hoff, d_hb, n_events, (uint64_t)max_interval_ns, d_out);
     NMZ_HIP(hipGetLastError());
-    NMZ_HIP(hipMemcpyAsync(delays, d_out, (uint64_t)n_events * 8, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    NMZ_TRY(copy_d2h(delays, d_out, n_events, st));
+    return call.done();
 }
 
 }  // extern "C"

@@ -594,21 +594,16 @@ int oq_build(OqState &o, const uint4 *d_table, uint32_t E, const ModParams &mod,
     std::vector<uint4> passes(np);
     for (size_t i = 0; i < np; ++i)
         passes[i] = make_uint4((uint32_t)o.passes[i].off16, (uint32_t)(o.passes[i].off16 >> 32), o.passes[i].rb16, 0);
-    const size_t need = Carve::bytes_for(off16, 16) + Carve::bytes_for(256 * np, 8) +
-                        Carve::bytes_for(oc.size(), sizeof(OqClass)) + Carve::bytes_for(tbl.size(), 16) +
-                        Carve::bytes_for(np, 16);
-    NMZ_TRY(o.mem.ensure(need));
-    Carve cv(o.mem.ptr);
-    o.d_blob = cv.take<uint4>(off16);
-    o.d_rowsum = cv.take<uint64_t>(256 * np);
-    o.d_classes = cv.take<OqClass>(oc.size());
-    uint4 *d_tbl = cv.take<uint4>(tbl.size());
-    uint4 *d_passes = cv.take<uint4>(np);
+    uint4 *d_tbl, *d_passes;
+    ScratchLayout lay;
+    lay.add(&o.d_blob, off16).add(&o.d_rowsum, 256 * np).add(&o.d_classes, oc.size()).add(&d_tbl, tbl.size());
+    lay.add(&d_passes, np);
+    NMZ_TRY(lay.bind(o.mem));
     NMZ_HIP(hipMemsetAsync(o.d_blob, 0, off16 * 16, st));
     NMZ_HIP(hipMemsetAsync(o.d_rowsum, 0, 256 * np * 8, st));
-    NMZ_HIP(hipMemcpyAsync(o.d_classes, oc.data(), oc.size() * sizeof(OqClass), hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_tbl, tbl.data(), tbl.size() * 16, hipMemcpyHostToDevice, st));
-    NMZ_HIP(hipMemcpyAsync(d_passes, passes.data(), np * 16, hipMemcpyHostToDevice, st));
+    NMZ_TRY(copy_h2d(o.d_classes, oc.data(), oc.size(), st));
+    NMZ_TRY(copy_h2d(d_tbl, tbl.data(), tbl.size(), st));
+    NMZ_TRY(copy_h2d(d_passes, passes.data(), np, st));
     hipLaunchKernelGGL(k_replayable_oq_levels, dim3((unsigned)tbl.size(), 256), dim3(256), 0, st, d_table, E, d_tbl,
                        o.d_classes, d_passes, o.d_blob, reinterpret_cast<unsigned long long *>(o.d_rowsum));
     NMZ_HIP(hipGetLastError());

@@ -380,10 +380,12 @@ __global__ __launch_bounds__(256) void k_replayable_sweep_general(
     }
 }
 
-static size_t partial_bytes(uint64_t S, uint32_t E) {
+// the per-chunk partial rows of a plan for S seeds and E events
+static int partial_bind(DevBuf &buf, uint64_t S, uint32_t E, uint4 **d_partial) {
     const uint64_t units = S / (64 * (uint64_t)REPLAY_U) + 257;
     const uint64_t chunks = (E + REPLAY_EC - 1) / REPLAY_EC;
-    return Carve::bytes_for(units * 64 * REPLAY_U * chunks, 16);
+    ScratchLayout lay;
+    return lay.add(d_partial, units * 64 * REPLAY_U * chunks).bind(buf);
 }
 
 int pd_sweep(nmz_replayable_plan *p, hipStream_t st, SeedScratch &sc, uint64_t S, nmz_sched_stats *d_stats) {
@@ -393,7 +395,8 @@ int pd_sweep(nmz_replayable_plan *p, hipStream_t st, SeedScratch &sc, uint64_t S
     if (p->mod.kind == MOD_FAST) {
         const uint64_t max_units = S / per_unit + 256;
         const uint32_t n_chunks = (E + REPLAY_EC - 1) / REPLAY_EC;
-        NMZ_TRY(p->partial.ensure(partial_bytes(p->max_seeds, E)));
+        uint4 *d_partial;
+        NMZ_TRY(partial_bind(p->partial, p->max_seeds, E, &d_partial));
         const uint64_t stride = (p->max_seeds / per_unit + 257) * (uint64_t)per_unit;
         // fold the u32 partial sums every 2^f groups of 4 events, (4 << f)(m - 1) + 3(m - 1) < 2^32
         uint32_t fold_mask = 0;
@@ -406,10 +409,10 @@ int pd_sweep(nmz_replayable_plan *p, hipStream_t st, SeedScratch &sc, uint64_t S
             hipLaunchKernelGGL(k_replayable_sweep_fast<REPLAY_U>, dim3(grid), dim3(256), 0, st, sc.b.units,
                                sc.b.n_units, sc.b.sorted_h0, p->d_table, E, p->d_classes, p->n_classes, p->mod.m,
                                p->mod.mu, p->mod.m_k64, REPLAY_EC, n_chunks, fold_mask, sc.counter,
-                               p->partial.as<uint4>(), stride);
+                               d_partial, stride);
         }
         hipLaunchKernelGGL(k_replayable_merge<REPLAY_U>, dim3(ceil_div(max_units * per_unit, 256)), dim3(256), 0, st,
-                           sc.b.units, sc.b.n_units, sc.b.sorted_idx, p->partial.as<uint4>(), stride, n_chunks,
+                           sc.b.units, sc.b.n_units, sc.b.sorted_idx, d_partial, stride, n_chunks,
                            d_stats);
     } else {
         KernelTimer kt(p->ctx, st, "replayable_sweep");

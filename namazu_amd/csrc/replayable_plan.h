@@ -26,25 +26,31 @@ constexpr uint32_t OQ_WG = 1024;
 struct SeedScratch {
     uint64_t *h0;
     Buckets b;
+    uint32_t *small;  // b's offset, n_units and total (buckets_small)
     uint32_t *counter;
 };
 
-inline size_t seed_scratch_bytes(uint64_t S) {
-    uint64_t max_units = S / REPLAY_SEEDS_PER_UNIT_MIN + 257;
-    return Carve::bytes_for(S, 8) * 2 + Carve::bytes_for(S, 4) + Carve::bytes_for(BUCKET_SMALL_U32, 4) +
-           Carve::bytes_for(bucket_hist_u32(S), 4) + Carve::bytes_for(max_units, 16) + Carve::bytes_for(4, 4);
+// the fields of a seed scratch for S seeds, appended to lay; seed_scratch_bind sizes a buffer for them,
+// carve_seed_scratch finds them again in a buffer that seed_scratch_bind sized for the same S
+inline void seed_scratch_layout(ScratchLayout &lay, uint64_t S, SeedScratch &s) {
+    lay.add(&s.h0, S).add(&s.b.sorted_h0, S).add(&s.b.sorted_idx, S).add(&s.small, BUCKET_SMALL_U32);
+    lay.add(&s.b.hist, bucket_hist_u32(S)).add(&s.b.units, S / REPLAY_SEEDS_PER_UNIT_MIN + 257).add(&s.counter, 4);
+}
+
+inline int seed_scratch_bind(DevBuf &buf, uint64_t S, SeedScratch &s) {
+    ScratchLayout lay;
+    seed_scratch_layout(lay, S, s);
+    NMZ_TRY(lay.bind(buf));
+    buckets_small(s.small, s.b);
+    return NMZ_OK;
 }
 
 inline SeedScratch carve_seed_scratch(void *p, uint64_t S) {
-    Carve cv(p);
+    ScratchLayout lay;
     SeedScratch s;
-    s.h0 = cv.take<uint64_t>(S);
-    s.b.sorted_h0 = cv.take<uint64_t>(S);
-    s.b.sorted_idx = cv.take<uint32_t>(S);
-    buckets_small(cv.take<uint32_t>(BUCKET_SMALL_U32), s.b);
-    s.b.hist = cv.take<uint32_t>(bucket_hist_u32(S));
-    s.b.units = cv.take<uint4>(S / REPLAY_SEEDS_PER_UNIT_MIN + 257);
-    s.counter = cv.take<uint32_t>(4);
+    seed_scratch_layout(lay, S, s);
+    (void)lay.place(p);
+    buckets_small(s.small, s.b);
     return s;
 }
 

@@ -161,13 +161,14 @@ int seeds_create_locked(nmz_ctx *ctx, const uint32_t *d_seed_off, const uint8_t 
     s->S = n_seeds;
     s->mem.pool = &ctx->pool;  // a stream of seed sets of one size reuses one buffer (no hipMalloc per set)
     hipStream_t st = ctx->stream;
-    const int rc = s->mem.ensure(seed_scratch_bytes(n_seeds) + Carve::bytes_for(bucket_hist_u32(n_seeds), 4));
+    ScratchLayout lay;  // a seed scratch, then the copy of its row counts
+    seed_scratch_layout(lay, n_seeds, s->sc);
+    const int rc = lay.add(&s->hist, bucket_hist_u32(n_seeds)).bind(s->mem);
     if (rc != NMZ_OK) {
         delete s;
         return rc;
     }
-    s->sc = carve_seed_scratch(s->mem.ptr, n_seeds);
-    s->hist = reinterpret_cast<uint32_t *>(static_cast<char *>(s->mem.ptr) + seed_scratch_bytes(n_seeds));
+    buckets_small(s->sc.small, s->sc.b);
     if (hipMemsetAsync(s->sc.counter, 0, 4 * sizeof(uint32_t), st) != hipSuccess ||
         seed_prefix_launch(st, d_seed_off, d_seed_bytes, dec_lo, n_seeds, s->sc.h0, s->sc.b.hist) != NMZ_OK ||
         hipMemcpyAsync(s->hist, s->sc.b.hist, bucket_hist_u32(n_seeds) * sizeof(uint32_t), hipMemcpyDeviceToDevice,

@@ -72,13 +72,11 @@ struct WtTopkScratch {
 };
 // the one carve of the scratch (p == nullptr: only the size is wanted)
 inline WtTopkScratch wt_topk_carve(void *p, uint64_t S) {
-    const size_t rec_off = Carve::bytes_for(1, sizeof(WtTopkState));
     WtTopkScratch s{};
-    s.bytes = rec_off + Carve::bytes_for(wt_max_chunks(S), sizeof(WtChunkRec));
-    if (p) {
-        s.tk = static_cast<WtTopkState *>(p);
-        s.rec = reinterpret_cast<WtChunkRec *>(static_cast<char *>(p) + rec_off);
-    }
+    ScratchLayout lay;
+    lay.add(&s.tk, 1).add(&s.rec, wt_max_chunks(S));
+    s.bytes = lay.bytes();
+    if (p) (void)lay.place(p);
     return s;
 }
 

@@ -697,8 +697,8 @@ bool wt_layout(WtState &w, nmz_ctx *ctx, uint32_t E, const ClassInfo *cls, uint3
 
 int wt_launch(WtState &w, const uint4 *d_table, uint32_t E, const ModParams &mod, hipStream_t st,
               const WtPlanHints *hints, WtClass *d_cls, unsigned long long *d_rowsum, bool sync) {
-    NMZ_TRY(w.mem.ensure(Carve::bytes_for(256 * (size_t)w.rb16, 16)));
-    w.d_blob = w.mem.as<uint4>();
+    ScratchLayout lay;
+    NMZ_TRY(lay.add(&w.d_blob, 256 * (size_t)w.rb16).bind(w.mem));
     w.d_rowsum = d_rowsum;
     w.d_classes = d_cls;
     WtHints hz{};
@@ -718,10 +718,10 @@ int wt_build(WtState &w, nmz_ctx *ctx, const uint4 *d_table, uint32_t E, const C
     std::vector<WtClass> oc;
     if (!wt_layout(w, ctx, E, cls, n_cls, mod, false, oc)) return NMZ_OK;
     // classes and row sums in their own buffer (the fused path uploads them with the plan's inputs)
-    NMZ_TRY(w.aux.ensure(Carve::bytes_for(256, 8) + Carve::bytes_for(oc.size(), sizeof(WtClass))));
-    Carve cv(w.aux.ptr);
-    unsigned long long *d_rowsum = cv.take<unsigned long long>(256);
-    WtClass *d_cls = cv.take<WtClass>(oc.size());
+    unsigned long long *d_rowsum;
+    WtClass *d_cls;
+    ScratchLayout lay;
+    NMZ_TRY(lay.add(&d_rowsum, 256).add(&d_cls, oc.size()).bind(w.aux));
     NMZ_HIP(hipMemsetAsync(d_rowsum, 0, 256 * 8, st));
     NMZ_TRY(ctx->pin[1].ensure(oc.size() * sizeof(WtClass)));
     std::memcpy(ctx->pin[1].ptr, oc.data(), oc.size() * sizeof(WtClass));

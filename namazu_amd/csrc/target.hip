@@ -461,24 +461,19 @@ static int target_plan_create_locked(nmz_ctx *ctx, const uint32_t *hint_off, con
             }
     }
     const size_t ns = max_seeds ? max_seeds : 1;
-    int rc = p->mem.ensure(Carve::bytes_for(table.size(), 8) + 2 * Carve::bytes_for(Gp, 8) +
-                           2 * Carve::bytes_for(Gp, 4) + Carve::bytes_for(Gp, 2) + Carve::bytes_for(slot.size(), 2) +
-                           Carve::bytes_for(ns, 8) + Carve::bytes_for(bucket_hist_u32(ns), 4));
+    uint64_t *d_table, *d_pn;
+    int64_t *d_arr;
+    uint32_t *d_orig, *d_pd;
+    uint16_t *d_ss, *d_slot;
+    ScratchLayout lay;
+    lay.add(&d_table, table.size()).add(&d_pn, Gp).add(&d_arr, Gp).add(&d_orig, Gp).add(&d_pd, Gp).add(&d_ss, Gp);
+    lay.add(&d_slot, slot.size()).add(&p->d_h0, ns).add(&p->d_rows, bucket_hist_u32(ns));
+    int rc = lay.bind(p->mem);
     if (rc != NMZ_OK) {
         p->mem.release();
         delete p;
         return rc;
     }
-    Carve cv(p->mem.ptr);
-    uint64_t *d_table = cv.take<uint64_t>(table.size());
-    uint64_t *d_pn = cv.take<uint64_t>(Gp);
-    int64_t *d_arr = cv.take<int64_t>(Gp);
-    uint32_t *d_orig = cv.take<uint32_t>(Gp);
-    uint32_t *d_pd = cv.take<uint32_t>(Gp);
-    uint16_t *d_ss = cv.take<uint16_t>(Gp);
-    uint16_t *d_slot = cv.take<uint16_t>(slot.size());
-    p->d_h0 = cv.take<uint64_t>(ns);
-    p->d_rows = cv.take<uint32_t>(bucket_hist_u32(ns));
     p->args = TgtArgs{p->d_h0, d_table, d_pn, d_arr, d_orig, d_ss, d_slot, d_pd, nullptr, 0, p->m, p->mu, G, p->net, K};
     hipStream_t st = ctx->stream;
     hipError_t e = hipMemcpyAsync(d_table, table.data(), table.size() * 8, hipMemcpyHostToDevice, st);
@@ -533,13 +528,10 @@ static int target_run(nmz_replayable_target_plan *p, hipStream_t st, const uint3
     nmz_topk_entry *d_lists = nullptr;
     if (k) {
         const size_t ns = p->max_seeds ? p->max_seeds : 1;
-        NMZ_TRY(p->scratch.ensure(Carve::bytes_for(ns, sizeof(nmz_target_stats)) +
-                                  Carve::bytes_for(ns, sizeof(nmz_sched_stats)) +
-                                  Carve::bytes_for(topk_scratch_entries(ns, 256), sizeof(nmz_topk_entry))));
-        Carve cv(p->scratch.ptr);
-        nmz_target_stats *own = cv.take<nmz_target_stats>(ns);
-        d_keys = cv.take<nmz_sched_stats>(ns);
-        d_lists = cv.take<nmz_topk_entry>(topk_scratch_entries(ns, 256));
+        nmz_target_stats *own;
+        ScratchLayout lay;
+        lay.add(&own, ns).add(&d_keys, ns).add(&d_lists, topk_scratch_entries(ns, 256));
+        NMZ_TRY(lay.bind(p->scratch));
         if (!d_stats) d_stats = own;
     }
     nmz_replayable_target_plan::Use *u = nullptr;
@@ -605,39 +597,30 @@ static int target_sweep_host(nmz_ctx *ctx, const uint32_t *seed_off, const uint8
     if (!topk) k = 0;
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
+    HostCall call(ctx);
     nmz_replayable_target_plan *plan = nullptr;
     NMZ_TRY(target_plan_create_locked(ctx, hint_off, hint_bytes, n_events, max_interval_ns, arrival_ns, entity,
                                       target_pos, n_seeds, &plan));
-    struct PlanGuard {
-        nmz_replayable_target_plan *p;
-        ~PlanGuard() { target_plan_destroy_locked(p); }
-    } pg{plan};
+    call.own_plan<target_plan_destroy_locked>(plan);
     if (n_counted) *n_counted = plan->n_counted;
     if (n_pairs) *n_pairs = plan->n_pairs;
     hipStream_t st = ctx->stream;
-    const uint64_t sbytes = (!decimal && n_seeds) ? seed_off[n_seeds] : 0;
-    NMZ_CHECK(sbytes == 0 || seed_bytes, "seed_bytes is NULL");
-    // shared with the delivery sweep's host form: both are synchronous and hold the context
-    NMZ_TRY(ctx->buf[16].ensure(Carve::bytes_for(n_seeds + 1, 4) + Carve::bytes_for(sbytes + 1, 1) +
-                                Carve::bytes_for(n_seeds + 1, sizeof(nmz_target_stats)) +
-                                Carve::bytes_for(k + 1, sizeof(nmz_topk_entry))));
-    Carve cv(ctx->buf[16].ptr);
-    uint32_t *d_soff = cv.take<uint32_t>(n_seeds + 1);
-    uint8_t *d_sb = cv.take<uint8_t>(sbytes + 1);
-    nmz_target_stats *d_stats = cv.take<nmz_target_stats>(n_seeds + 1);
-    nmz_topk_entry *d_tk = cv.take<nmz_topk_entry>(k + 1);
-    if (!decimal && n_seeds) {
-        NMZ_HIP(hipMemcpyAsync(d_soff, seed_off, (n_seeds + 1) * 4, hipMemcpyHostToDevice, st));
-        if (sbytes) NMZ_HIP(hipMemcpyAsync(d_sb, seed_bytes, sbytes, hipMemcpyHostToDevice, st));
-    }
+    uint64_t sbytes;
+    NMZ_TRY(seed_csr_bytes(seed_off, seed_bytes, n_seeds, decimal, &sbytes));
+    uint32_t *d_soff;
+    uint8_t *d_sb;
+    nmz_target_stats *d_stats;
+    nmz_topk_entry *d_tk;
+    ScratchLayout lay;
+    lay.add(&d_soff, n_seeds + 1).add(&d_sb, sbytes + 1).add(&d_stats, n_seeds + 1).add(&d_tk, k + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_TARGET_DELIVERY_HOST]));
+    NMZ_TRY(upload_seeds(d_soff, d_sb, seed_off, seed_bytes, n_seeds, decimal, st));
     // the rank mode is checked even when there is nothing to rank
     NMZ_TRY(target_run(plan, st, decimal ? nullptr : d_soff, d_sb, seed_lo, n_seeds, decimal ? seed_lo : 0, rank_mode,
                        k, (stats || !k) ? d_stats : nullptr, d_tk));
-    if (stats && n_seeds)
-        NMZ_HIP(hipMemcpyAsync(stats, d_stats, n_seeds * sizeof(nmz_target_stats), hipMemcpyDeviceToHost, st));
-    if (k) NMZ_HIP(hipMemcpyAsync(topk, d_tk, k * sizeof(nmz_topk_entry), hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    if (stats) NMZ_TRY(copy_d2h(stats, d_stats, n_seeds, st));
+    NMZ_TRY(copy_d2h(topk, d_tk, k, st));
+    return call.done();
 }
 
 }  // namespace nmz

@@ -225,7 +225,9 @@ extern "C" int nmz_topk_select_dev(nmz_ctx *ctx, const nmz_sched_stats *d_stats,
     CtxGuard g(ctx);
     NMZ_TRY(g.rc);
     if (k == 0) return NMZ_OK;
-    NMZ_TRY(ctx->buf[5].ensure(topk_scratch_entries(n, k) * sizeof(nmz_topk_entry) + 256));
-    return topk_select(stream ? (hipStream_t)stream : ctx->stream, d_stats, n, seed0, k,
-                       ctx->buf[5].as<nmz_topk_entry>(), d_out);
+    // one field, sized in entries plus a spare 256 bytes: not a layout, whose rounding would change the size
+    DevBuf &scr = ctx->buf[SLOT_TOPK];
+    NMZ_TRY(scr.ensure(topk_scratch_entries(n, k) * sizeof(nmz_topk_entry) + 256));
+    return topk_select(stream ? (hipStream_t)stream : ctx->stream, d_stats, n, seed0, k, scr.as<nmz_topk_entry>(),
+                       d_out);
 }

@@ -265,7 +265,7 @@ __global__ void k_sig_first(const uint32_t *__restrict__ idx_sorted, const uint3
 
 // the per-context rank-key table (RANK_KEYS entries), built on first use; the caller holds ctx
 int sig_rank_keys(nmz_ctx *ctx, const ulonglong2 **out) {
-    DevBuf &kb = ctx->buf[14];  // rank keys, built once per context
+    DevBuf &kb = ctx->rank_keys;
     if (!kb.ptr) {
         NMZ_TRY(kb.ensure((size_t)RANK_KEYS * sizeof(ulonglong2)));
         // on the context's stream, waited for once: later launches on any stream see the finished table
@@ -312,15 +312,13 @@ int classes_launch(nmz_ctx *ctx, const uint64_t *d_sig, uint32_t N, uint32_t *d_
                                                (uint32_t *)nullptr, (uint32_t *)nullptr, (int)N, 0, 64, st));
     NMZ_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                               hipcub::Max(), (int)N, st));
-    DevBuf &scr = ctx->buf[6];
-    NMZ_TRY(scr.ensure(4 * Carve::bytes_for(N, 8) + 4 * Carve::bytes_for(N, 4) +
-                       Carve::bytes_for(std::max(sort_bytes, scan_bytes) + 1, 1)));
-    Carve cv(scr.ptr);
-    uint64_t *lo = cv.take<uint64_t>(N), *hi = cv.take<uint64_t>(N);
-    uint64_t *k1 = cv.take<uint64_t>(N), *k2 = cv.take<uint64_t>(N);
-    uint32_t *idx = cv.take<uint32_t>(N), *v1 = cv.take<uint32_t>(N), *v2 = cv.take<uint32_t>(N);
-    uint32_t *start = cv.take<uint32_t>(N);
-    void *tmp = cv.take<char>(std::max(sort_bytes, scan_bytes) + 1);
+    uint64_t *lo, *hi, *k1, *k2;
+    uint32_t *idx, *v1, *v2, *start;
+    char *tmp;
+    ScratchLayout lay;
+    lay.add(&lo, N).add(&hi, N).add(&k1, N).add(&k2, N).add(&idx, N).add(&v1, N).add(&v2, N).add(&start, N);
+    lay.add(&tmp, std::max(sort_bytes, scan_bytes) + 1);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_CLASSES]));
     const unsigned g = ceil_div(N, 256);
     hipLaunchKernelGGL(k_sig_split, dim3(g), dim3(256), 0, st, d_sig, N, lo, hi, idx);
     NMZ_HIP(hipGetLastError());
@@ -441,13 +439,13 @@ int device_unique_u64(const uint64_t *d_sym, uint64_t total, uint64_t *d_uniq, u
     NMZ_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,
                                               (int)cap + 1, 0, 64, st));
     DevBuf scr;
-    NMZ_TRY(scr.ensure(Carve::bytes_for(DS_G_SLOTS, 8) + Carve::bytes_for(4, 4) + Carve::bytes_for(cap + 1, 8) +
-                       Carve::bytes_for(sort_bytes + 1, 1)));
-    Carve cv(scr.ptr);
-    unsigned long long *tab = cv.take<unsigned long long>(DS_G_SLOTS);
-    uint32_t *flags = cv.take<uint32_t>(4);
-    uint64_t *raw = cv.take<uint64_t>(cap + 1);
-    void *tmp = cv.take<char>(sort_bytes + 1);
+    unsigned long long *tab;
+    uint32_t *flags;
+    uint64_t *raw;
+    char *tmp;
+    ScratchLayout lay;
+    lay.add(&tab, DS_G_SLOTS).add(&flags, 4).add(&raw, cap + 1).add(&tmp, sort_bytes + 1);
+    NMZ_TRY(lay.bind(scr));
     int rc = NMZ_OK;
     uint32_t hf[4] = {0, 0, 0, 0};
     auto ok = [&](hipError_t e) {
@@ -507,20 +505,17 @@ int nmz_trace_signatures(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym,
         for (uint64_t i = 0; i < total; ++i)
             if (entity[i] != NMZ_NONE) max_ent = std::max(max_ent, entity[i] + 1);
     hipStream_t st = ctx->stream;
-    NMZ_TRY(ctx->buf[7].ensure(Carve::bytes_for(n_traces + 1, 8) + Carve::bytes_for(total + 1, 8) +
-                               Carve::bytes_for(total + 1, 4) + Carve::bytes_for(2 * (uint64_t)n_traces, 8)));
-    Carve cv(ctx->buf[7].ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n_traces + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    uint32_t *d_ent = cv.take<uint32_t>(total + 1);
-    uint64_t *d_sig = cv.take<uint64_t>(2 * (uint64_t)n_traces);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, (n_traces + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, sym, total * 8, hipMemcpyHostToDevice, st));
-    if (total && entity) NMZ_HIP(hipMemcpyAsync(d_ent, entity, total * 4, hipMemcpyHostToDevice, st));
+    HostCall call(ctx);
+    uint64_t *d_off, *d_sym, *d_sig;
+    uint32_t *d_ent;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_ent, total + 1).add(&d_sig, 2 * (uint64_t)n_traces);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_UNIQUE_HOST]));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    if (entity) NMZ_TRY(copy_h2d(d_ent, entity, total, st));
     NMZ_TRY(sig_launch(ctx, d_off, d_sym, entity ? d_ent : nullptr, n_traces, max_ent, d_sig, st));
-    NMZ_HIP(hipMemcpyAsync(sig, d_sig, 2 * (uint64_t)n_traces * 8, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    NMZ_TRY(copy_d2h(sig, d_sig, 2 * (uint64_t)n_traces, st));
+    return call.done();
 }
 
 int nmz_unique_traces(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
@@ -536,26 +531,22 @@ int nmz_unique_traces(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, co
         for (uint64_t i = 0; i < total; ++i)
             if (entity[i] != NMZ_NONE) max_ent = std::max(max_ent, entity[i] + 1);
     hipStream_t st = ctx->stream;
-    NMZ_TRY(ctx->buf[7].ensure(Carve::bytes_for(n_traces + 1, 8) + Carve::bytes_for(total + 1, 8) +
-                               Carve::bytes_for(total + 1, 4) + Carve::bytes_for(2 * (uint64_t)n_traces, 8) +
-                               Carve::bytes_for(n_traces, 4)));
-    Carve cv(ctx->buf[7].ptr);
-    uint64_t *d_off = cv.take<uint64_t>(n_traces + 1);
-    uint64_t *d_sym = cv.take<uint64_t>(total + 1);
-    uint32_t *d_ent = cv.take<uint32_t>(total + 1);
-    uint64_t *d_sig = cv.take<uint64_t>(2 * (uint64_t)n_traces);
-    uint32_t *d_first = cv.take<uint32_t>(n_traces);
-    NMZ_HIP(hipMemcpyAsync(d_off, off, (n_traces + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total) NMZ_HIP(hipMemcpyAsync(d_sym, sym, total * 8, hipMemcpyHostToDevice, st));
-    if (total && entity) NMZ_HIP(hipMemcpyAsync(d_ent, entity, total * 4, hipMemcpyHostToDevice, st));
+    HostCall call(ctx);
+    uint64_t *d_off, *d_sym, *d_sig;
+    uint32_t *d_ent, *d_first;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_ent, total + 1).add(&d_sig, 2 * (uint64_t)n_traces);
+    lay.add(&d_first, n_traces);
+    NMZ_TRY(lay.bind(ctx->buf[SLOT_UNIQUE_HOST]));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    if (entity) NMZ_TRY(copy_h2d(d_ent, entity, total, st));
     NMZ_TRY(sig_launch(ctx, d_off, d_sym, entity ? d_ent : nullptr, n_traces, max_ent, d_sig, st));
     {
         KernelTimer kt(ctx, st, "unique_classes");
         NMZ_TRY(classes_launch(ctx, d_sig, n_traces, d_first, st));
     }
-    NMZ_HIP(hipMemcpyAsync(first_equal, d_first, (uint64_t)n_traces * 4, hipMemcpyDeviceToHost, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    return NMZ_OK;
+    NMZ_TRY(copy_d2h(first_equal, d_first, n_traces, st));
+    return call.done();
 }
 
 int nmz_unique_traces_dev(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_entity,

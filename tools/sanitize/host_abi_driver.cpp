@@ -4,13 +4,16 @@
 // opening failing cleanly when no device is present. Exit status 0 = every check held.
 #include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/nmz_gpu.h"
+#include "../../namazu_amd/csrc/scratch_layout.h"
 
 static std::atomic<int> g_fail{0};
 #define CHECK(c)                                                                   \
@@ -505,6 +508,120 @@ static void moves_cases() {
                                nullptr) == NMZ_EINVAL);
 }
 
+// ScratchLayout (scratch_layout.h) over a host buffer that holds exactly the bytes asked for: under ASan a field
+// that reached past the buffer, or a write through a pointer that was never placed, is an error
+struct FakeBuf {
+    void *ptr = nullptr;
+    size_t cap = 0;
+    const char *slot = nullptr;
+    bool busy = false;
+    int ensures = 0;
+    int ensure(size_t bytes) {
+        ++ensures;
+        std::free(ptr);
+        ptr = std::malloc(bytes);
+        cap = bytes;
+        return ptr ? NMZ_OK : NMZ_ENOMEM;
+    }
+    ~FakeBuf() { std::free(ptr); }
+};
+
+template <typename T>
+static size_t rounded(size_t count) { return (count * sizeof(T) + 255) & ~size_t(255); }
+
+static void layout_cases() {
+    static_assert(sizeof(nmz_proc_attr) == 16 && sizeof(nmz_topk_entry) == 24, "the 16- and 24-byte element types");
+    {  // mixed element sizes: offsets, total, and a write of every field's full extent
+        uint8_t *a;
+        uint16_t *b;
+        uint32_t *c;
+        uint64_t *d;
+        nmz_proc_attr *e;
+        nmz_topk_entry *f;
+        nmz_move_counts *g;
+        const size_t n[7] = {3, 129, 65, 33, 17, 11, 5};
+        nmz::ScratchLayout lay;
+        lay.add(&a, n[0]).add(&b, n[1]).add(&c, n[2]).add(&d, n[3]).add(&e, n[4]).add(&f, n[5]).add(&g, n[6]);
+        const size_t want[7] = {rounded<uint8_t>(n[0]),       rounded<uint16_t>(n[1]),       rounded<uint32_t>(n[2]),
+                                rounded<uint64_t>(n[3]),      rounded<nmz_proc_attr>(n[4]),  rounded<nmz_topk_entry>(n[5]),
+                                rounded<nmz_move_counts>(n[6])};
+        size_t sum = 0;
+        for (size_t w : want) sum += w;
+        CHECK(lay.bytes() == sum);
+        FakeBuf buf;
+        CHECK(lay.bind(buf) == NMZ_OK && buf.ensures == 1 && buf.cap == sum);
+        char *base = static_cast<char *>(buf.ptr);
+        char *at[7] = {(char *)a, (char *)b, (char *)c, (char *)d, (char *)e, (char *)f, (char *)g};
+        size_t off = 0;
+        for (int i = 0; i < 7; ++i) {
+            CHECK(at[i] == base + off && off % 256 == 0);
+            CHECK(i == 0 || at[i] > at[i - 1]);
+            off += want[i];
+        }
+        std::memset(a, 1, n[0] * sizeof *a);
+        std::memset(b, 2, n[1] * sizeof *b);
+        std::memset(c, 3, n[2] * sizeof *c);
+        std::memset(d, 4, n[3] * sizeof *d);
+        std::memset(e, 5, n[4] * sizeof *e);
+        std::memset(f, 6, n[5] * sizeof *f);
+        std::memset(g, 7, n[6] * sizeof *g);
+        // no field reached into its neighbour: each one's first and last byte still hold its own value
+        CHECK(a[0] == 1 && b[0] == 0x0202 && ((char *)c)[n[2] * 4 - 1] == 3 && ((char *)g)[0] == 7);
+        CHECK(((char *)f)[n[5] * 24 - 1] == 6 && ((char *)e)[0] == 5 && ((char *)d)[n[3] * 8 - 1] == 4);
+    }
+    {  // a zero-count field takes no space and has the address of the field after it, or of the buffer's end
+        uint64_t *x, *z_mid, *y, *z_end;
+        nmz::ScratchLayout lay;
+        lay.add(&x, 10).add(&z_mid, 0).add(&y, 40).add(&z_end, 0);
+        CHECK(lay.bytes() == rounded<uint64_t>(10) + rounded<uint64_t>(40));
+        FakeBuf buf;
+        CHECK(lay.bind(buf) == NMZ_OK);
+        char *base = static_cast<char *>(buf.ptr);
+        CHECK((char *)z_mid == (char *)y && (char *)y == base + 256);
+        CHECK((char *)z_end == base + lay.bytes());
+        std::memset(x, 0, 10 * 8);
+        std::memset(y, 0, 40 * 8);
+    }
+    {  // one field more than the capacity: an error, no allocation, no pointer written
+        uint32_t *p[nmz::ScratchLayout::CAP + 1];
+        for (auto &q : p) q = reinterpret_cast<uint32_t *>(0x10);
+        nmz::ScratchLayout lay;
+        for (auto &q : p) lay.add(&q, 4);
+        FakeBuf buf;
+        CHECK(lay.bind(buf) == NMZ_EINVAL && buf.ensures == 0 && buf.ptr == nullptr);
+        CHECK(std::strstr(nmz_last_error(), "fields") != nullptr);
+        CHECK(lay.place(nullptr) == NMZ_EINVAL);
+        for (auto &q : p) CHECK(q == reinterpret_cast<uint32_t *>(0x10));
+    }
+    {  // count * sizeof(T), its rounding, and the running sum must not wrap
+        uint64_t *p;
+        uint8_t *q, *r;
+        FakeBuf buf;
+        nmz::ScratchLayout mul, rnd, sum;
+        CHECK(mul.add(&p, SIZE_MAX / 4).bind(buf) == NMZ_ENOMEM);
+        CHECK(rnd.add(&q, SIZE_MAX - 100).bind(buf) == NMZ_ENOMEM);
+        CHECK(sum.add(&q, SIZE_MAX / 2).add(&r, SIZE_MAX / 2 + 512).bind(buf) == NMZ_ENOMEM);
+        CHECK(buf.ensures == 0);
+    }
+    {  // a named slot is marked while a layout is bound to it: a second bind is refused, by name
+        FakeBuf buf;
+        buf.slot = "SLOT_DRIVER_TEST";
+        uint32_t *p, *q;
+        {
+            nmz::ScratchLayout outer;
+            CHECK(outer.add(&p, 8).bind(buf) == NMZ_OK && buf.busy);
+            nmz::ScratchLayout inner;
+            CHECK(inner.add(&q, 8000).bind(buf) == NMZ_EINVAL && buf.ensures == 1);
+            CHECK(std::strstr(nmz_last_error(), "SLOT_DRIVER_TEST") != nullptr);
+            std::memset(p, 0, 8 * 4);  // the outer pointer is still good
+        }
+        CHECK(!buf.busy);
+        nmz::ScratchLayout again;
+        CHECK(again.add(&q, 8000).bind(buf) == NMZ_OK && buf.ensures == 2);
+        std::memset(q, 0, 8000 * 4);
+    }
+}
+
 static void no_device_cases() {
     nmz_ctx *c = reinterpret_cast<nmz_ctx *>(0x1);
     int rc = nmz_open(0, &c);
@@ -557,6 +674,7 @@ int main() {
     match_cases();
     align_cases();
     moves_cases();
+    layout_cases();
     no_device_cases();
     thread_local_errors(8, 2000);
     if (g_fail) {
