@@ -968,6 +968,52 @@ int nmz_ed_align_pairs_dev(nmz_ed_align_plan *plan, const uint64_t *d_off, const
 int nmz_ed_align_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
                        const uint32_t *pairs, uint64_t n_pairs, uint32_t band, uint32_t *dist, nmz_edit_op *ops);
 
+/* ---- edit scripts over wider bands: 0 <= band <= NMZ_ALIGN_WIDE_MAX_BAND ------------------------------------
+ * The same build-defined extension (historystorage/historystorage.go:50-51; the reference has equality only,
+ * naive/naive.go:235-257; util/trace/trace.go:29-31), with the semantics above word for word: dist = min(Lev, band +
+ * 1), the canonical alignment for dist <= band, `band` slots per pair, sentinels behind the ops, nmz_edit_op as it
+ * is. The script does not depend on the band once Lev <= band, so a pair with Lev <= 64 gets at any wide band the ops
+ * that the narrow form gives at band 64. Every band 0 .. 1024 is accepted: for band <= NMZ_ALIGN_MAX_BAND these
+ * entry points return byte for byte what their narrow counterparts return (they run the same kernel), beyond it
+ * k_ed_align_wide does the work. Limits, each NMZ_EINVAL with a message, checked before any device work (arguments
+ * before the context): band <= NMZ_ALIGN_WIDE_MAX_BAND (wider bands are not built yet); traces shorter than 2^32 - 1
+ * elements; pair indexes < n_traces; offsets non-decreasing; n_pairs * band fits the output. n_pairs == 0 is legal
+ * and needs no device; band == 0 is legal (ops may be NULL). The nmz_ed_align_* and nmz_move_profile* entry points
+ * keep NMZ_ALIGN_MAX_BAND. */
+#define NMZ_ALIGN_WIDE_MAX_BAND 1024
+/* One pair on the calling host thread, no device work (historystorage.go:50-51, naive.go:235-257,
+ * util/trace/trace.go:29-31): nmz_ed_align_host's plain +inf-banded DP with 16-bit cells (they hold band + 1 <=
+ * 1025), its band rows kept whole -- (n + 1) * (2 band + 1) * 2 bytes, NMZ_ENOMEM with the sizes when they do not
+ * fit -- then the walk by the definition. It shares no table, scan or packed history with the kernels: the check of
+ * the device forms. */
+int nmz_ed_align_wide_host(const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m, uint32_t band,
+                           uint32_t *dist, nmz_edit_op *ops /* [band] */);
+/* The plan owns the history scratch (historystorage.go:50-51, naive.go:235-257, util/trace/trace.go:29-31): 2 bits
+ * per band cell and row (the band's cells rounded up to 256 * {1, 2, 3, 5, 9}: 64 .. 576 bytes per row), for `slots`
+ * pairs in flight of up to max_len elements each, 256 MiB at the most in all -- at band 1024 about 466,000 rows. A
+ * max_len whose single pair exceeds that is NMZ_EINVAL naming both numbers. The plan serves one stream at a time (a
+ * launch on another stream waits for the one before); destroy waits for its launches. */
+typedef struct nmz_ed_align_wide_plan nmz_ed_align_wide_plan;
+int nmz_ed_align_wide_plan_create(nmz_ctx *ctx, uint32_t band, uint64_t max_len, nmz_ed_align_wide_plan **out);
+int nmz_ed_align_wide_plan_destroy(nmz_ed_align_wide_plan *plan);
+/* The plan's constants (historystorage.go:50-51, naive.go:235-257, util/trace/trace.go:29-31): the pairs in flight
+ * and the bytes of history scratch behind them; each pointer may be NULL. */
+int nmz_ed_align_wide_plan_info(const nmz_ed_align_wide_plan *plan, uint32_t *slots, uint64_t *history_bytes);
+/* Device CSR and device pairs in, d_dist[n_pairs] and d_ops[n_pairs * band] out (historystorage.go:50-51,
+ * naive.go:235-257, util/trace/trace.go:29-31); one launch enqueued on `stream` (NULL = the context's), nothing
+ * else. The host cannot read the offsets: they must be non-decreasing and stay inside d_sym, the pair indexes below
+ * the number of traces (a decreasing pair of offsets reads as an empty trace), and a pair with a trace longer than
+ * the plan's max_len gets dist = NMZ_NONE and sentinel ops. */
+int nmz_ed_align_wide_pairs_dev(nmz_ed_align_wide_plan *plan, const uint64_t *d_off, const uint64_t *d_sym,
+                                const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist,
+                                nmz_edit_op *d_ops /* [n_pairs * band] */, void *stream);
+/* Host pointers, synchronous, built on the _dev form (historystorage.go:50-51, naive.go:235-257,
+ * util/trace/trace.go:29-31): a plan for the longest trace of the pairs given + upload + launch + download. The
+ * device buffers are taken for the call from the context's pool. pairs[2 * n_pairs], dist[n_pairs],
+ * ops[n_pairs * band]. */
+int nmz_ed_align_wide_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
+                            const uint32_t *pairs, uint64_t n_pairs, uint32_t band, uint32_t *dist, nmz_edit_op *ops);
+
 /* ---- move profiles: which events move between the runs of many pairs ----------------------------------------
  * A build-defined extension of the same optional interface (historystorage/historystorage.go:50-51; the reference has
  * equality only, naive/naive.go:235-257; the labels of failing and passing runs naive.go:199-213). Input: the scripts

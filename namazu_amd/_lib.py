@@ -76,6 +76,7 @@ EDIT_OP_DTYPE = np.dtype([("a_pos", "<u4"), ("b_pos", "<u4"), ("kind", "<u4")])
 assert EDIT_OP_DTYPE.itemsize == 12
 NMZ_EDIT_SUB, NMZ_EDIT_DEL, NMZ_EDIT_INS = 0, 1, 2
 NMZ_ALIGN_MAX_BAND = 64
+NMZ_ALIGN_WIDE_MAX_BAND = 1024  # the nmz_ed_align_wide_* entry points
 # move profiles: one table symbol's counters (nmz_move_counts) and the call's totals (nmz_move_info)
 MOVE_COUNTS_DTYPE = np.dtype([("later", "<u4"), ("earlier", "<u4"), ("dropped", "<u4"), ("extra", "<u4"),
                               ("sub_from", "<u4"), ("sub_to", "<u4"), ("n_pairs", "<u4"), ("reserved", "<u4"),
@@ -173,6 +174,12 @@ SIGNATURES = {
     "nmz_ed_align_plan_info": (_int, [_P, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
     "nmz_ed_align_pairs_dev": (_int, [_P, _P, _P, _P, _u64, _P, _P, _P]),
     "nmz_ed_align_pairs": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P]),
+    "nmz_ed_align_wide_host": (_int, [_P, _u64, _P, _u64, _u32, _P, _P]),
+    "nmz_ed_align_wide_plan_create": (_int, [_P, _u32, _u64, ctypes.POINTER(_P)]),
+    "nmz_ed_align_wide_plan_destroy": (_int, [_P]),
+    "nmz_ed_align_wide_plan_info": (_int, [_P, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
+    "nmz_ed_align_wide_pairs_dev": (_int, [_P, _P, _P, _P, _u64, _P, _P, _P]),
+    "nmz_ed_align_wide_pairs": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P]),
     "nmz_script_moves_host": (_int, [_P, _u64, _P, _u64, _P, _u32, _P]),
     "nmz_move_profile_host": (_int, [_P, _P, _u32, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P]),
     "nmz_move_profile_dev": (_int, [_P, _P, _P, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P, _int, _P]),

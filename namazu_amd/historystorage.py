@@ -237,15 +237,17 @@ class Naive(HistoryStorage):
 
     def DiffSimilar(self, trace, k, band):
         """SearchSimilar, then what differs: [(id, distance, script)] for the neighbours within the band, script the
-        ops (EDIT_OP_DTYPE rows) that turn the stored run `id` into `trace` -- one edit_scripts call for all of them.
-        script_moves(stored, trace, script) names the events delivered earlier or later."""
+        ops (EDIT_OP_DTYPE rows) that turn the stored run `id` into `trace` -- one edit_scripts call for all of them
+        (edit_scripts_wide for 64 < band <= 1024). script_moves(stored, trace, script) names the events delivered
+        earlier or later."""
         t = trace.symbols if isinstance(trace, SingleTrace) else np.asarray(trace, np.uint64)
         near = [(i, d) for i, d in self.SearchSimilar(trace, k, band) if d <= band]
         if not near:
             return []
         ts = TraceSet([self._index.ts.trace(i) for i, _ in near] + [t])
         pairs = np.array([[r, len(near)] for r in range(len(near))], np.uint32)
-        es = edit_scripts(ts, pairs, band, ctx=self._index.ctx)
+        align = edit_scripts if band <= _lib.NMZ_ALIGN_MAX_BAND else edit_scripts_wide
+        es = align(ts, pairs, band, ctx=self._index.ctx)
         return [(i, d, es.script(r).copy()) for r, (i, d) in enumerate(near)]
 
     def DiffFailing(self, band, k=1, ctx=None):
@@ -779,10 +781,75 @@ def edit_script_host(a, b, band):
     return dist.value, (ops[:dist.value] if dist.value <= band else None)
 
 
+class AlignWidePlan:
+    """AlignPlan for every band 0 .. 1024 (nmz_ed_align_wide_plan): beyond 64 the history scratch of
+    k_ed_align_wide, up to 64 a narrow plan behind the same calls."""
+
+    def __init__(self, band, max_len, ctx=None):
+        self.ctx = ctx or _lib.default_context()
+        self.band = int(band)
+        self.plan = ctypes.c_void_p()
+        L = _lib.load()
+        _lib.check(L.nmz_ed_align_wide_plan_create(self.ctx.handle, self.band, int(max_len), ctypes.byref(self.plan)))
+        s, h = ctypes.c_uint32(), ctypes.c_uint64()
+        _lib.check(L.nmz_ed_align_wide_plan_info(self.plan, ctypes.byref(s), ctypes.byref(h)))
+        self.slots, self.history_bytes = s.value, h.value
+
+    def pairs_dev(self, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops, stream=None):
+        """AlignPlan.pairs_dev's arguments and results, ops[n_pairs][band] with band up to 1024."""
+        _lib.check(_lib.load().nmz_ed_align_wide_pairs_dev(
+            self.plan, ctypes.c_void_p(d_off), ctypes.c_void_p(d_sym), ctypes.c_void_p(d_pairs), int(n_pairs),
+            ctypes.c_void_p(d_dist), ctypes.c_void_p(d_ops), ctypes.c_void_p(stream) if stream else None))
+
+    def close(self):
+        if self.plan:
+            _lib.load().nmz_ed_align_wide_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def edit_scripts_wide(ts, pairs, band, ctx=None):
+    """edit_scripts for every band 0 .. 1024 (nmz_ed_align_wide_pairs): the same EditScripts, ops of shape
+    [P][band]. A pair within 64 edits gets the ops edit_scripts gives at band 64; a band <= 64 gives edit_scripts'
+    bytes."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = int(band)
+    if not 0 <= band < 2**32:
+        raise ValueError(f"band = {band} does not fit uint32")
+    dist = np.zeros(len(pairs), np.uint32)
+    ops = np.zeros((len(pairs), min(band, _lib.NMZ_ALIGN_WIDE_MAX_BAND)), _lib.EDIT_OP_DTYPE)
+    ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_WIDE_MAX_BAND else None)
+    _lib.check(_lib.load().nmz_ed_align_wide_pairs(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
+                                                   len(ts), _lib.ptr(pairs), len(pairs), band, _lib.ptr(dist),
+                                                   _lib.ptr(ops) if ops.size else None))
+    return EditScripts(dist, ops, band)
+
+
+def edit_script_wide_host(a, b, band):
+    """edit_script_host for every band 0 .. 1024 (nmz_ed_align_wide_host, no GPU): (dist, script | None). The same
+    plain banded matrix with 16-bit cells; the reference of edit_scripts_wide."""
+    a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+    b = np.ascontiguousarray(b, np.uint64).reshape(-1)
+    band = int(band)
+    if not 0 <= band < 2**32:
+        raise ValueError(f"band = {band} does not fit uint32")
+    dist = ctypes.c_uint32()
+    ops = np.zeros(min(band, _lib.NMZ_ALIGN_WIDE_MAX_BAND), _lib.EDIT_OP_DTYPE)
+    _lib.check(_lib.load().nmz_ed_align_wide_host(_lib.ptr(a), len(a), _lib.ptr(b), len(b), band, ctypes.byref(dist),
+                                                  _lib.ptr(ops) if ops.size else None))
+    return dist.value, (ops[:dist.value] if dist.value <= band else None)
+
+
 def script_moves(a, b, ops):
     """The events a script moved: the k-th DEL of a symbol value pairs with the k-th INS of that value, in script
     order. Returns [(symbol, a_pos, b_pos)]: a[a_pos] was delivered at b_pos of b instead. DELs and INSs without a
-    partner (an event missing or extra) and SUBs are not moves."""
+    partner (an event missing or extra) and SUBs are not moves. Plain Python over the ops given: a script of any
+    length, edit_scripts_wide's included."""
     dels, inss = {}, {}
     for o in ops:
         k = int(o["kind"])
