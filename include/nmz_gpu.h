@@ -37,7 +37,7 @@
  *   nmz_ed_align_*         -> the same interface, extended: the edit script between
  *                             two traces (which events moved, are missing or were
  *                             replaced); an empty script <=> SingleTrace.Equals.
- *   nmz_script_moves_host / nmz_move_profile* / nmz_ed_diff_profile -> the same
+ *   nmz_script_moves_host / nmz_move_profile* / nmz_ed_diff_profile* -> the same
  *                             interface once more: the scripts of many pairs tallied per
  *                             event symbol (delivered later, earlier, dropped, extra).
  *
@@ -978,8 +978,9 @@ int nmz_ed_align_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, u
  * k_ed_align_wide does the work. Limits, each NMZ_EINVAL with a message, checked before any device work (arguments
  * before the context): band <= NMZ_ALIGN_WIDE_MAX_BAND (wider bands are not built yet); traces shorter than 2^32 - 1
  * elements; pair indexes < n_traces; offsets non-decreasing; n_pairs * band fits the output. n_pairs == 0 is legal
- * and needs no device; band == 0 is legal (ops may be NULL). The nmz_ed_align_* and nmz_move_profile* entry points
- * keep NMZ_ALIGN_MAX_BAND. */
+ * and needs no device; band == 0 is legal (ops may be NULL). The nmz_ed_align_*, nmz_move_profile{_host, _dev,} and
+ * nmz_ed_diff_profile entry points keep NMZ_ALIGN_MAX_BAND; nmz_move_profile_wide* and nmz_ed_diff_profile_wide
+ * (below) tally these scripts. */
 #define NMZ_ALIGN_WIDE_MAX_BAND 1024
 /* One pair on the calling host thread, no device work (historystorage.go:50-51, naive.go:235-257,
  * util/trace/trace.go:29-31): nmz_ed_align_host's plain +inf-banded DP with 16-bit cells (they hold band + 1 <=
@@ -1089,6 +1090,54 @@ int nmz_move_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uin
 int nmz_ed_diff_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
                         const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint64_t *usym, uint64_t n_usym,
                         uint32_t *dist /* may be NULL */, nmz_move_counts *counts, nmz_move_info *info);
+
+/* ---- move profiles over wider bands: 0 <= band <= NMZ_ALIGN_WIDE_MAX_BAND ----------------------------------------
+ * The same build-defined extension (historystorage/historystorage.go:50-51; naive/naive.go:235-257; the labels
+ * naive.go:199-213), with the semantics above word for word over the scripts nmz_ed_align_wide_* gives: names,
+ * partners, direction, span, nmz_move_counts, nmz_move_info, n_unknown, n_beyond for dist > band or dist ==
+ * NMZ_NONE, partner[n_pairs * band] with NMZ_NONE wherever a slot has no partner. Every band 0 .. 1024 is accepted:
+ * for band <= NMZ_ALIGN_MAX_BAND these entry points return byte for byte what their narrow counterparts return (they
+ * run the same kernel), beyond it k_script_moves_wide does the work. Limits of the host-pointer forms, each
+ * NMZ_EINVAL with a message, checked before any device work (arguments before the context): band <=
+ * NMZ_ALIGN_WIDE_MAX_BAND; n_pairs * band < 2^32 (at band 1024 just under 4 Mi pairs); everything
+ * nmz_ed_align_wide_pairs checks, with its messages; usym strictly increasing; where ops are an input, for the first
+ * dist slots of every script: kind <= 2, a_pos < n for DEL / SUB, b_pos < m for INS / SUB (the message names pair and
+ * slot). n_pairs == 0 is legal and needs no device: the counters and the info are zero. nmz_script_moves_host takes a
+ * script of any length as it is. */
+/* The whole profile on the calling host thread, plain loops, no device work (historystorage.go:50-51,
+ * naive.go:199-213, 235-257): nmz_move_profile_host's body behind the wider band limit, for callers without a device,
+ * and the check of the device forms (it shares nothing with the kernels). dist[n_pairs] and ops[n_pairs * band] as
+ * nmz_ed_align_wide_pairs writes them; partner[n_pairs * band] may be NULL. */
+int nmz_move_profile_wide_host(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                               uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
+                               const uint64_t *usym, uint64_t n_usym, uint32_t *partner /* may be NULL */,
+                               nmz_move_counts *counts /* [n_usym] */, nmz_move_info *info);
+/* Device pointers in and out (historystorage.go:50-51, naive.go:199-213, 235-257); enqueued on `stream` (NULL = the
+ * context's). accumulate as for nmz_move_profile_dev: 0 clears d_counts[n_usym] and d_info on that stream first,
+ * otherwise the call adds to them. Apart from the clear it enqueues one launch and allocates nothing. The host
+ * cannot read the inputs: n_pairs * band < 2^32 and d_usym strictly increasing are the caller's to keep, offsets and
+ * pairs as for nmz_ed_align_wide_pairs_dev; an op of a script with kind > 2 or a position outside its trace counts
+ * for nothing (no name, no partner), and the kernel makes no out-of-range read for it. d_partner[n_pairs * band] may
+ * be NULL. */
+int nmz_move_profile_wide_dev(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_pairs,
+                              uint64_t n_pairs, uint32_t band, const uint32_t *d_dist, const nmz_edit_op *d_ops,
+                              const uint64_t *d_usym, uint64_t n_usym, uint32_t *d_partner /* may be NULL */,
+                              nmz_move_counts *d_counts, nmz_move_info *d_info, int accumulate, void *stream);
+/* Host pointers, synchronous, built on the _dev form (historystorage.go:50-51, naive.go:199-213, 235-257): the
+ * scripts are given; upload + launch + download. The device buffers are taken for the call from the context's
+ * pool. partner may be NULL. */
+int nmz_move_profile_wide(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
+                          const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint32_t *dist,
+                          const nmz_edit_op *ops, const uint64_t *usym, uint64_t n_usym,
+                          uint32_t *partner /* may be NULL */, nmz_move_counts *counts, nmz_move_info *info);
+/* From the traces to the profile (historystorage.go:50-51, naive.go:199-213, 235-257): the CSR goes up, the pairs
+ * are aligned (k_ed_align_wide on a plan taken for the call from the context's pool) and profiled on the device;
+ * only dist (may be NULL), counts and info come back, the ops never leave the device. The result is byte-identical
+ * to nmz_move_profile_wide over nmz_ed_align_wide_pairs' output. */
+int nmz_ed_diff_profile_wide(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces,
+                             const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint64_t *usym,
+                             uint64_t n_usym, uint32_t *dist /* may be NULL */, nmz_move_counts *counts,
+                             nmz_move_info *info);
 
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),

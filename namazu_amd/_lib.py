@@ -185,6 +185,10 @@ SIGNATURES = {
     "nmz_move_profile_dev": (_int, [_P, _P, _P, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P, _int, _P]),
     "nmz_move_profile": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P]),
     "nmz_ed_diff_profile": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _u64, _P, _P, _P]),
+    "nmz_move_profile_wide_host": (_int, [_P, _P, _u32, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P]),
+    "nmz_move_profile_wide_dev": (_int, [_P, _P, _P, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P, _int, _P]),
+    "nmz_move_profile_wide": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _P, _P, _u64, _P, _P, _P]),
+    "nmz_ed_diff_profile_wide": (_int, [_P, _P, _P, _u32, _P, _u64, _u32, _P, _u64, _P, _P, _P]),
     "nmz_replayable_delivery_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
     "nmz_replayable_delivery_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),
     "nmz_replayable_delivery_plan_destroy": (_int, [_P]),

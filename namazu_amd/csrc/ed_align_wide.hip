@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "ed_plan.h"
 #include "nmz_common.h"
 #include "nmz_internal.h"
 
@@ -299,7 +300,7 @@ struct nmz_ed_align_wide_plan {
 
 namespace nmz {
 
-static int aw_band(uint32_t band) {
+int aw_band(uint32_t band) {
     NMZ_CHECK(band <= NMZ_ALIGN_WIDE_MAX_BAND, "band " + std::to_string(band) +
                                                    " exceeds NMZ_ALIGN_WIDE_MAX_BAND (1024): edit scripts over wider "
                                                    "bands are not built yet");
@@ -312,9 +313,8 @@ static int aw_len(const std::string &what, uint64_t len) {
 }
 
 // every limit of nmz_ed_align_wide_pairs, no device; *max_len = the longest trace of the pairs
-static int aw_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
-                       uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
-                       uint64_t *max_len) {
+int aw_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs,
+                uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, uint64_t *max_len) {
     NMZ_TRY(aw_band(band));
     *max_len = 0;
     if (n_pairs == 0) return NMZ_OK;
@@ -334,7 +334,7 @@ static int aw_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_trac
 }
 
 // the plan's shape for (band, max_len): no device. A band <= 64 has the narrow plan's shape.
-static int aw_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
+int aw_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
     NMZ_TRY(aw_band(band));
     if (band <= NMZ_ALIGN_MAX_BAND) return align_shape(band, max_len, slot_words);
     NMZ_TRY(aw_len("a trace of max_len", max_len));
@@ -345,7 +345,7 @@ static int aw_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
     return NMZ_OK;
 }
 
-static void aw_plan_destroy_locked(nmz_ed_align_wide_plan *p) {
+void aw_plan_destroy_locked(nmz_ed_align_wide_plan *p) {
     if (p->narrow) align_plan_destroy_locked(p->narrow);
     if (p->ev) {
         (void)hipEventSynchronize(p->ev);
@@ -355,8 +355,8 @@ static void aw_plan_destroy_locked(nmz_ed_align_wide_plan *p) {
     delete p;
 }
 
-static int aw_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_t slot_words,
-                                 nmz_ed_align_wide_plan **out) {
+int aw_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_t slot_words,
+                          nmz_ed_align_wide_plan **out) {
     auto *p = new nmz_ed_align_wide_plan();
     p->ctx = ctx;
     p->band = band;
@@ -385,8 +385,8 @@ static int aw_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, 
     return NMZ_OK;
 }
 
-static int aw_enqueue(nmz_ed_align_wide_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
-                      const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops) {
+int aw_enqueue(nmz_ed_align_wide_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
+               const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops) {
     if (p->narrow) return align_enqueue(p->narrow, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops);
     NMZ_CHECK(n_pairs <= (SIZE_MAX / sizeof(nmz_edit_op)) / NMZ_ALIGN_WIDE_MAX_BAND,
               "n_pairs * band does not fit the output");

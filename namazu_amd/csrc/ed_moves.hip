@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "ed_plan.h"
 #include "nmz_common.h"
 #include "nmz_internal.h"
 
@@ -35,42 +36,14 @@ namespace nmz {
 constexpr uint32_t MV_WAVES = 4;                  // pairs in flight per workgroup
 constexpr uint32_t MV_THREADS = 64 * MV_WAVES;
 constexpr uint32_t MV_BLOCKS_PER_CU = 8;          // 8 waves per SIMD
-constexpr uint64_t MV_LDS_SYMS = 2048;            // the table is staged in LDS up to this size (16 KiB)
-constexpr uint64_t MV_MISS = ~0ull;
 static_assert(NMZ_ALIGN_MAX_BAND == 64, "a pair's ops fit one wave: one slot per lane");
 static_assert(sizeof(nmz_move_counts) == 48 && sizeof(nmz_move_info) == 32, "the ABI's record sizes");
-
-struct MvArgs {
-    const uint64_t *off, *sym;
-    const uint32_t *pairs;
-    uint64_t n_pairs;
-    uint32_t band;
-    const uint32_t *dist;
-    const nmz_edit_op *ops;
-    const uint64_t *usym;
-    uint64_t n_usym;
-    uint32_t *partner;  // may be NULL
-    nmz_move_counts *counts;
-    nmz_move_info *info;
-};
 
 // lane t's value, t wave-uniform: two v_readlane, no LDS
 __device__ __forceinline__ uint64_t mv_lane64(uint64_t v, uint32_t t) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)t);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)t);
     return ((uint64_t)hi << 32) | lo;
-}
-
-// index of v in the strictly increasing tab[U], MV_MISS if absent; the trip count depends on U alone
-__device__ __forceinline__ uint64_t mv_find(const uint64_t *tab, uint64_t U, uint64_t v) {
-    if (U == 0) return MV_MISS;
-    uint64_t lo = 0, n = U;
-    while (n > 1) {
-        const uint64_t h = n >> 1;
-        lo = tab[lo + h] <= v ? lo + h : lo;
-        n -= h;
-    }
-    return tab[lo] == v ? lo : MV_MISS;
 }
 
 template <bool LDS>
@@ -204,7 +177,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_script_moves(const MvArgs g) {
 // ---- the host side ------------------------------------------------------------------------------------------------
 
 // one live op against its traces
-static int moves_op_check(const nmz_edit_op &o, uint64_t n, uint64_t m, const std::string &where) {
+int moves_op_check(const nmz_edit_op &o, uint64_t n, uint64_t m, const std::string &where) {
     NMZ_CHECK(o.kind <= NMZ_EDIT_INS, "op kind " + std::to_string(o.kind) + " is not SUB, DEL or INS (" + where + ")");
     NMZ_CHECK(o.kind == NMZ_EDIT_INS || o.a_pos < n,
               "a_pos " + std::to_string(o.a_pos) + " is outside a trace of " + std::to_string(n) + " elements (" + where +
@@ -217,19 +190,19 @@ static int moves_op_check(const nmz_edit_op &o, uint64_t n, uint64_t m, const st
 
 // every limit of the host-pointer profile forms, no device. ops == nullptr with want_ops == false: the scripts are
 // made on the device (nmz_ed_diff_profile)
-static int moves_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
-                          uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, bool want_ops,
-                          const uint64_t *usym, uint64_t n_usym, const nmz_move_counts *counts,
-                          const nmz_move_info *info, uint64_t *max_len) {
-    // nmz_ed_diff_profile has no ops and an optional dist: align_validate only asks whether they are there
+int moves_validate(MvBandCheck band_ok, MvAlignValidate validate, const uint64_t *off, const uint64_t *sym,
+                   uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint32_t *dist,
+                   const nmz_edit_op *ops, bool want_ops, const uint64_t *usym, uint64_t n_usym,
+                   const nmz_move_counts *counts, const nmz_move_info *info, uint64_t *max_len) {
+    // nmz_ed_diff_profile* has no ops and an optional dist: the validator only asks whether they are there
     const uint32_t some_dist = 0;
     const nmz_edit_op some_op{};
-    NMZ_TRY(align_band(band));
+    NMZ_TRY(band_ok(band));
     NMZ_CHECK(n_pairs * (uint64_t)band < (1ull << 32) && (band == 0 || n_pairs < (1ull << 32)),
               "n_pairs * band = " + std::to_string(n_pairs) + " * " + std::to_string(band) + " must stay below 2^32: a "
               "uint32 counter could wrap");
-    NMZ_TRY(align_validate(off, sym, n_traces, pairs, n_pairs, band, want_ops || dist ? dist : &some_dist,
-                           want_ops ? ops : &some_op, max_len));
+    NMZ_TRY(validate(off, sym, n_traces, pairs, n_pairs, band, want_ops || dist ? dist : &some_dist,
+                     want_ops ? ops : &some_op, max_len));
     NMZ_CHECK(n_usym == 0 || (usym && counts), "usym or counts is NULL");
     NMZ_CHECK(info != nullptr, "info is NULL");
     for (uint64_t u = 1; u < n_usym; ++u)
@@ -248,8 +221,7 @@ static int moves_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_t
 
 // partner[n_ops] by the definition: per value the queue of its DEL slots and the queue of its INS slots, in script
 // order; the r-th of one is the partner of the r-th of the other. The ops are live and inside their traces.
-static void moves_partners(const uint64_t *a, const uint64_t *b, const nmz_edit_op *ops, uint32_t n_ops,
-                           uint32_t *partner) {
+void moves_partners(const uint64_t *a, const uint64_t *b, const nmz_edit_op *ops, uint32_t n_ops, uint32_t *partner) {
     std::map<uint64_t, std::vector<uint32_t>> dels, inss;
     for (uint32_t s = 0; s < n_ops; ++s) {
         partner[s] = NMZ_NONE;
@@ -266,7 +238,7 @@ static void moves_partners(const uint64_t *a, const uint64_t *b, const nmz_edit_
     }
 }
 
-static int moves_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate) {
+int moves_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate) {
     NMZ_TRY(align_band(a.band));
     NMZ_CHECK(a.n_pairs * (uint64_t)a.band < (1ull << 32) && (a.band == 0 || a.n_pairs < (1ull << 32)),
               "n_pairs * band = " + std::to_string(a.n_pairs) + " * " + std::to_string(a.band) + " must stay below "
@@ -292,37 +264,20 @@ static int moves_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accu
     return NMZ_OK;
 }
 
-static void moves_zero(nmz_move_counts *counts, uint64_t n_usym, nmz_move_info *info) {
+void moves_zero(nmz_move_counts *counts, uint64_t n_usym, nmz_move_info *info) {
     for (uint64_t u = 0; u < n_usym; ++u) counts[u] = nmz_move_counts{};
     *info = nmz_move_info{};
 }
 
-}  // namespace nmz
-
-using namespace nmz;
-
-extern "C" {
-
-// One script on the calling thread (historystorage.go:50-51, naive.go:235-257): the definition, nothing shared with
-// the kernel.
-int nmz_script_moves_host(const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m, const nmz_edit_op *ops,
-                          uint32_t n_ops, uint32_t *partner) {
-    NMZ_CHECK((n == 0 || a) && (m == 0 || b), "a or b is NULL");
-    NMZ_CHECK(n_ops == 0 || (ops && partner), "ops or partner is NULL");
-    for (uint32_t s = 0; s < n_ops; ++s) NMZ_TRY(moves_op_check(ops[s], n, m, "slot " + std::to_string(s)));
-    moves_partners(a, b, ops, n_ops, partner);
-    return NMZ_OK;
-}
-
-// The whole profile on the calling thread (historystorage.go:50-51, naive.go:199-213, 235-257): plain loops, a set
-// of the names per script, std::lower_bound into the table.
-int nmz_move_profile_host(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
-                          uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
-                          const uint64_t *usym, uint64_t n_usym, uint32_t *partner, nmz_move_counts *counts,
-                          nmz_move_info *info) {
+// the profile by the definition, for any band the validator lets through: plain loops, a set of the names per
+// script, std::lower_bound into the table. Nothing shared with the kernels.
+int moves_profile_host(MvBandCheck band_ok, MvAlignValidate validate, const uint64_t *off, const uint64_t *sym,
+                       uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint32_t *dist,
+                       const nmz_edit_op *ops, const uint64_t *usym, uint64_t n_usym, uint32_t *partner,
+                       nmz_move_counts *counts, nmz_move_info *info) {
     uint64_t max_len = 0;
-    NMZ_TRY(moves_validate(off, sym, n_traces, pairs, n_pairs, band, dist, ops, true, usym, n_usym, counts, info,
-                           &max_len));
+    NMZ_TRY(moves_validate(band_ok, validate, off, sym, n_traces, pairs, n_pairs, band, dist, ops, true, usym, n_usym,
+                           counts, info, &max_len));
     moves_zero(counts, n_usym, info);
     auto find = [&](uint64_t v) -> nmz_move_counts * {
         const uint64_t *at = std::lower_bound(usym, usym + n_usym, v);
@@ -384,6 +339,33 @@ int nmz_move_profile_host(const uint64_t *off, const uint64_t *sym, uint32_t n_t
     return NMZ_OK;
 }
 
+}  // namespace nmz
+
+using namespace nmz;
+
+extern "C" {
+
+// One script on the calling thread (historystorage.go:50-51, naive.go:235-257): the definition, nothing shared with
+// the kernel.
+int nmz_script_moves_host(const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m, const nmz_edit_op *ops,
+                          uint32_t n_ops, uint32_t *partner) {
+    NMZ_CHECK((n == 0 || a) && (m == 0 || b), "a or b is NULL");
+    NMZ_CHECK(n_ops == 0 || (ops && partner), "ops or partner is NULL");
+    for (uint32_t s = 0; s < n_ops; ++s) NMZ_TRY(moves_op_check(ops[s], n, m, "slot " + std::to_string(s)));
+    moves_partners(a, b, ops, n_ops, partner);
+    return NMZ_OK;
+}
+
+// The whole profile on the calling thread (historystorage.go:50-51, naive.go:199-213, 235-257): plain loops, a set
+// of the names per script, std::lower_bound into the table.
+int nmz_move_profile_host(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                          uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
+                          const uint64_t *usym, uint64_t n_usym, uint32_t *partner, nmz_move_counts *counts,
+                          nmz_move_info *info) {
+    return moves_profile_host(align_band, align_validate, off, sym, n_traces, pairs, n_pairs, band, dist, ops, usym,
+                              n_usym, partner, counts, info);
+}
+
 int nmz_move_profile_dev(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_pairs,
                          uint64_t n_pairs, uint32_t band, const uint32_t *d_dist, const nmz_edit_op *d_ops,
                          const uint64_t *d_usym, uint64_t n_usym, uint32_t *d_partner, nmz_move_counts *d_counts,
@@ -401,8 +383,8 @@ int nmz_move_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uin
                      nmz_move_info *info) {
     // the arguments first: they are checked without a device
     uint64_t max_len = 0;
-    NMZ_TRY(moves_validate(off, sym, n_traces, pairs, n_pairs, band, dist, ops, true, usym, n_usym, counts, info,
-                           &max_len));
+    NMZ_TRY(moves_validate(align_band, align_validate, off, sym, n_traces, pairs, n_pairs, band, dist, ops, true, usym,
+                           n_usym, counts, info, &max_len));
     if (n_pairs == 0) {  // all zero: no device either
         moves_zero(counts, n_usym, info);
         return NMZ_OK;
@@ -443,8 +425,8 @@ int nmz_ed_diff_profile(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, 
                         uint32_t *dist, nmz_move_counts *counts, nmz_move_info *info) {
     // the arguments first: they are checked without a device
     uint64_t max_len = 0, slot_words = 0;
-    NMZ_TRY(moves_validate(off, sym, n_traces, pairs, n_pairs, band, dist, nullptr, false, usym, n_usym, counts, info,
-                           &max_len));
+    NMZ_TRY(moves_validate(align_band, align_validate, off, sym, n_traces, pairs, n_pairs, band, dist, nullptr, false,
+                           usym, n_usym, counts, info, &max_len));
     if (n_pairs == 0) {  // all zero: no device either
         moves_zero(counts, n_usym, info);
         return NMZ_OK;

@@ -1,8 +1,10 @@
 // K3 (edit distance) declarations shared by its translation units: the plan, the kernels' argument structs and the
 // entry points of ed_build.hip (plan builders), ed_tp.hip (two-phase search), ed_bv.hip and ed_wide.hip (kernels).
-// ed.hip holds k_ed_tile, the generic kernel, the k-NN list kernels, the search's dispatch and the C ABI.
+// ed.hip holds k_ed_tile, the generic kernel, the k-NN list kernels, the search's dispatch and the C ABI. Also here:
+// what ed_moves_wide.hip (K9w) takes from ed_align_wide.hip (K8w's host helpers) and shares with ed_moves.hip (K9).
 #pragma once
 #include <memory>
+#include <string>
 #include <unordered_map>
 
 #include "nmz_common.h"
@@ -154,6 +156,75 @@ int ed_wide_launch(const EdWideArgs &A, uint32_t band, hipStream_t st);
 // stored traces of A; in-band results into A.knn + q * k
 int ed_wide_query_launch(const EdWideArgs &A, uint32_t band, const uint32_t *qpeq, uint64_t qstride,
                          const uint32_t *qlen, uint32_t n_q, hipStream_t st);
+
+// ---- edit scripts over wide bands (ed_align_wide.hip), for ed_moves_wide.hip ----
+// aw_validate: every limit of nmz_ed_align_wide_pairs, no device; *max_len = the longest trace of the pairs.
+// aw_shape: the plan's shape for (band, max_len), no device. The _locked forms and aw_enqueue want the caller to
+// hold the context.
+int aw_band(uint32_t band);
+int aw_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs,
+                uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, uint64_t *max_len);
+int aw_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words);
+int aw_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_t slot_words,
+                          nmz_ed_align_wide_plan **out);
+void aw_plan_destroy_locked(nmz_ed_align_wide_plan *p);
+int aw_enqueue(nmz_ed_align_wide_plan *p, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
+               const uint32_t *d_pairs, uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops);
+
+// ---- move profiles: what K9 (ed_moves.hip) and K9w (ed_moves_wide.hip) share ----
+constexpr uint64_t MV_LDS_SYMS = 2048;  // the table is staged in LDS up to this size (16 KiB)
+constexpr uint64_t MV_MISS = ~0ull;
+
+struct MvArgs {
+    const uint64_t *off, *sym;
+    const uint32_t *pairs;
+    uint64_t n_pairs;
+    uint32_t band;
+    const uint32_t *dist;
+    const nmz_edit_op *ops;
+    const uint64_t *usym;
+    uint64_t n_usym;
+    uint32_t *partner;  // may be NULL
+    nmz_move_counts *counts;
+    nmz_move_info *info;
+};
+
+// index of v in the strictly increasing tab[U], MV_MISS if absent; the trip count depends on U alone
+__device__ __forceinline__ uint64_t mv_find(const uint64_t *tab, uint64_t U, uint64_t v) {
+    if (U == 0) return MV_MISS;
+    uint64_t lo = 0, n = U;
+    while (n > 1) {
+        const uint64_t h = n >> 1;
+        lo = tab[lo + h] <= v ? lo + h : lo;
+        n -= h;
+    }
+    return tab[lo] == v ? lo : MV_MISS;
+}
+
+// the band check and the aligner's validator of a profile form: align_band / align_validate (band <= 64) or
+// aw_band / aw_validate (band <= 1,024)
+typedef int (*MvBandCheck)(uint32_t band);
+typedef int (*MvAlignValidate)(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                               uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops,
+                               uint64_t *max_len);
+// one live op against its traces
+int moves_op_check(const nmz_edit_op &o, uint64_t n, uint64_t m, const std::string &where);
+// every limit of the host-pointer profile forms, no device. ops == nullptr with want_ops == false: the scripts are
+// made on the device (nmz_ed_diff_profile*)
+int moves_validate(MvBandCheck band_ok, MvAlignValidate validate, const uint64_t *off, const uint64_t *sym,
+                   uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint32_t *dist,
+                   const nmz_edit_op *ops, bool want_ops, const uint64_t *usym, uint64_t n_usym,
+                   const nmz_move_counts *counts, const nmz_move_info *info, uint64_t *max_len);
+// partner[n_ops] by the definition; the ops are live and inside their traces
+void moves_partners(const uint64_t *a, const uint64_t *b, const nmz_edit_op *ops, uint32_t n_ops, uint32_t *partner);
+void moves_zero(nmz_move_counts *counts, uint64_t n_usym, nmz_move_info *info);
+// the body of nmz_move_profile_host and nmz_move_profile_wide_host: the whole profile on the calling thread
+int moves_profile_host(MvBandCheck band_ok, MvAlignValidate validate, const uint64_t *off, const uint64_t *sym,
+                       uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint32_t *dist,
+                       const nmz_edit_op *ops, const uint64_t *usym, uint64_t n_usym, uint32_t *partner,
+                       nmz_move_counts *counts, nmz_move_info *info);
+// K9's launch (band <= 64) behind its argument checks and the clear; the caller holds the context
+int moves_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate);
 
 }  // namespace nmz
 

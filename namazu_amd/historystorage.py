@@ -252,8 +252,9 @@ class Naive(HistoryStorage):
 
     def DiffFailing(self, band, k=1, ctx=None):
         """Which events are delivered later, earlier, dropped or extra in this storage's failing runs, each measured
-        against its k nearest passing runs (move_profile). The runs are loaded and labelled as OrderContrast does it
-        (IsSuccessful, naive.go:199-213; a run whose result cannot be read is skipped, cli/tools/summary.go:47-51). A
+        against its k nearest passing runs (move_profile; move_profile_wide for 64 < band <= 1024). The runs are
+        loaded and labelled as OrderContrast does it (IsSuccessful, naive.go:199-213; a run whose result cannot be
+        read is skipped, cli/tools/summary.go:47-51). A
         SimilarityIndex over the passing runs answers the failing runs' queries; the pairs are (a = passing
         neighbour, b = failing run) for the neighbours within the band, so "later" reads "delivered later in the
         failing run". Returns the MoveProfile of one move_profile call, its .pairs the stored-run ids behind the
@@ -280,7 +281,8 @@ class Naive(HistoryStorage):
                 if j != _lib.NMZ_NONE and d <= band]
         ts = TraceSet([t for _, t in passing] + [t for _, t in failing])
         pairs = np.array([[j, len(passing) + f] for j, f in near], np.uint32).reshape(-1, 2)
-        prof = move_profile(ts, pairs, band, ctx=index.ctx)
+        profile = move_profile if band <= _lib.NMZ_ALIGN_MAX_BAND else move_profile_wide
+        prof = profile(ts, pairs, band, ctx=index.ctx)
         prof.pairs = np.array([[passing[j][0], failing[f][0]] for j, f in near], np.uint32).reshape(-1, 2)
         return prof
 
@@ -957,4 +959,48 @@ def move_profile_of(ts, pairs, es, ctx=None, usym=None, want_partner=False, host
     else:
         ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_MAX_BAND else None)
         _lib.check(_lib.load().nmz_move_profile(ctx.handle if ctx else None, *args))
+    return MoveProfile(usym, counts, info[0], dist, partner)
+
+
+def move_profile_wide(ts, pairs, band, ctx=None, usym=None):
+    """move_profile for every band 0 .. 1024 (nmz_ed_diff_profile_wide): the pairs are aligned as edit_scripts_wide
+    aligns them and tallied on the device; the ops never come to the host. The same MoveProfile; a band <= 64 gives
+    move_profile's bytes."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = _move_band(band)
+    usym = _move_table(ts, usym)
+    dist = np.zeros(len(pairs), np.uint32)
+    counts = np.zeros(len(usym), _lib.MOVE_COUNTS_DTYPE)
+    info = np.zeros(1, _lib.MOVE_INFO_DTYPE)
+    ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_WIDE_MAX_BAND else None)
+    _lib.check(_lib.load().nmz_ed_diff_profile_wide(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
+                                                    len(ts), _lib.ptr(pairs), len(pairs), band, _lib.ptr(usym),
+                                                    len(usym), _lib.ptr(dist),
+                                                    _lib.ptr(counts) if len(usym) else None, _lib.ptr(info)))
+    return MoveProfile(usym, counts, info[0], dist)
+
+
+def move_profile_of_wide(ts, pairs, es, ctx=None, usym=None, want_partner=False, host=False):
+    """move_profile_of for every band 0 .. 1024 (es: edit_scripts_wide's result over the same ts and pairs), through
+    nmz_move_profile_wide -- or, with host=True, through nmz_move_profile_wide_host on the calling thread (no GPU).
+    want_partner adds partner[P][band]."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = _move_band(es.band)
+    usym = _move_table(ts, usym)
+    dist = np.ascontiguousarray(es.dist, np.uint32).reshape(-1)
+    ops = np.ascontiguousarray(es.ops, _lib.EDIT_OP_DTYPE)
+    if len(dist) != len(pairs) or ops.shape != (len(pairs), min(band, _lib.NMZ_ALIGN_WIDE_MAX_BAND)):
+        raise ValueError(f"scripts of shape {ops.shape} for {len(pairs)} pairs at band {band}")
+    counts = np.zeros(len(usym), _lib.MOVE_COUNTS_DTYPE)
+    info = np.zeros(1, _lib.MOVE_INFO_DTYPE)
+    partner = np.full(ops.shape, _lib.NMZ_NONE, np.uint32) if want_partner else None
+    args = (_lib.ptr(ts.off), _lib.ptr(ts.sym), len(ts), _lib.ptr(pairs), len(pairs), band, _lib.ptr(dist),
+            _lib.ptr(ops) if ops.size else None, _lib.ptr(usym), len(usym),
+            _lib.ptr(partner) if want_partner and partner.size else None, _lib.ptr(counts) if len(usym) else None,
+            _lib.ptr(info))
+    if host:
+        _lib.check(_lib.load().nmz_move_profile_wide_host(*args))
+    else:
+        ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_WIDE_MAX_BAND else None)
+        _lib.check(_lib.load().nmz_move_profile_wide(ctx.handle if ctx else None, *args))
     return MoveProfile(usym, counts, info[0], dist, partner)

@@ -506,6 +506,28 @@ static void moves_cases() {
     CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
     CHECK(nmz_move_profile_dev(nullptr, off, sym.data(), pairs, 2, 2, dist, ops.data(), usym, 2, partner, counts, &info, 0,
                                nullptr) == NMZ_EINVAL);
+    // the wide forms: the same rotation through band 70 (6 sentinel slots behind the 64 ops), then the refusals
+    std::vector<nmz_edit_op> o70(70);
+    std::vector<uint32_t> p70(70, 7);
+    uint32_t d70 = 0;
+    CHECK(nmz_ed_align_wide_host(a.data(), a.size(), b.data(), b.size(), 70, &d70, o70.data()) == NMZ_OK && d70 == 64);
+    CHECK(nmz_move_profile_wide_host(off2, both.data(), 2, fwd, 1, 70, &d70, o70.data(), &x, 1, p70.data(), &cx, &info) ==
+          NMZ_OK);
+    CHECK(cx.later == 32 && cx.n_pairs == 1 && cx.span_later == 32 * 66 + 496 && p70[63] == 31 && p70[69] == NONE);
+    CHECK(info.n_scripts == 1 && info.n_ops == 64);
+    CHECK(nmz_move_profile_wide_host(off2, both.data(), 2, fwd, 1, 1025, &d70, o70.data(), &x, 1, p70.data(), &cx,
+                                     &info) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "NMZ_ALIGN_WIDE_MAX_BAND") != nullptr);
+    o70[40].kind = 7;
+    CHECK(nmz_move_profile_wide_host(off2, both.data(), 2, fwd, 1, 70, &d70, o70.data(), &x, 1, p70.data(), &cx, &info) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "pair 0, slot 40") != nullptr);
+    CHECK(nmz_move_profile_wide(nullptr, nullptr, nullptr, 0, nullptr, 0, 512, nullptr, nullptr, &x, 1, nullptr, &cx,
+                                &info) == NMZ_OK && cx.later == 0);
+    CHECK(nmz_ed_diff_profile_wide(nullptr, off2, both.data(), 2, fwd, 1, 512, &x, 1, nullptr, &cx, &info) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    CHECK(nmz_move_profile_wide_dev(nullptr, off2, both.data(), fwd, 1, 512, &d70, o70.data(), &x, 1, nullptr, &cx, &info,
+                                    0, nullptr) == NMZ_EINVAL);
 }
 
 // ScratchLayout (scratch_layout.h) over a host buffer that holds exactly the bytes asked for: under ASan a field
