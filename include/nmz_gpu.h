@@ -1139,6 +1139,85 @@ int nmz_ed_diff_profile_wide(nmz_ctx *ctx, const uint64_t *off, const uint64_t *
                              uint64_t n_usym, uint32_t *dist /* may be NULL */, nmz_move_counts *counts,
                              nmz_move_info *info);
 
+/* ---- edit scripts and move profiles per entity: the partial-order view of a diff -----------------------------
+ * The same build-defined extension (historystorage/historystorage.go:50-51; the reference has equality only,
+ * naive/naive.go:235-257) in the reference's partial-order mode (cli/tools/visualize.go:62-136, createTracesPerEntity
+ * and tracesEqualInPO; `visualize`'s po_reduction defaults to true). Inputs: the CSR off / sym and entity[N] (uint32),
+ * parallel to sym: ids global to the store (equal ids in two traces mean the same entity -- unlike nmz_unique_traces,
+ * whose ids are dense per trace), each < n_entities or NMZ_NONE for an action without an event (skipped, as
+ * nmz_unique_traces skips it); 1 <= n_entities <= NMZ_PO_MAX_ENTITIES; a band 0 .. NMZ_ALIGN_WIDE_MAX_BAND.
+ *   Projection. t|g is the subsequence of trace t's elements with entity g, in order; src_g(t)[p] the index in t of
+ *               its p-th element; lift_g(t, p) = src_g(t)[p] for p < |t|g|, and |t| for p = |t|g|.
+ *   Distance.   dist = min(sum over g of Lev(a|g, b|g), band + 1): exact (one Lev_g > band puts the sum beyond it).
+ *               dist == 0 <=> the entity sets and every per-entity sequence are equal <=> tracesEqualInPO.
+ *   Script.     For dist <= band exactly dist ops: for g = 0, 1, ... in ascending id the canonical script of
+ *               (a|g, b|g) as defined above, every a_pos replaced by lift_g(a, a_pos) and every b_pos by
+ *               lift_g(b, b_pos), concatenated in entity order; sentinels in the remaining slots. The entity of an op
+ *               is entity_a[a_pos] for DEL / SUB and entity_b[b_pos] for INS. Within one entity's segment the slots
+ *               keep script order; positions are not monotone across segments.
+ * The lifted ops satisfy what nmz_move_profile_wide* validates, and those kernels assume no position order: the move
+ * profile of a PO script is what nmz_move_profile_wide_host returns for it over the original CSR. With n_entities == 1
+ * and no NMZ_NONE the entry points return byte for byte what nmz_ed_align_wide_* return. Limits, each NMZ_EINVAL with
+ * a message, checked before any device work (arguments before the context): everything nmz_ed_align_wide_pairs
+ * checks, with its messages; entity non-NULL when there is any element; 1 <= n_entities <= NMZ_PO_MAX_ENTITIES; every
+ * id < n_entities or NMZ_NONE (the message names the element); n_traces * n_entities < 2^31 - 1 (the projected traces
+ * are indexed with 32 bits). n_pairs == 0 needs no device; band == 0 is legal with ops NULL. */
+#define NMZ_PO_MAX_ENTITIES 1024
+/* Device pointers in and out (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136): the stable partition
+ * of every trace by entity, enqueued on `stream` (NULL = the context's): a count pass, one scan, a scatter pass.
+ * d_poff[n_traces * n_entities + 1] (uint64): projected trace t * n_entities + g is d_psym[d_poff[.] .. d_poff[. +
+ * 1]), an ordinary CSR; d_psrc[q] (uint32) is the index in its trace of the element at d_psym[q]. d_psym and d_psrc
+ * hold as many elements as d_sym. The host cannot read the ids: NMZ_NONE and, here, ids >= n_entities are dropped and
+ * never indexed with. The scan's temporary is a scratch slot of the context. */
+int nmz_po_project_dev(nmz_ctx *ctx, const uint64_t *d_off, const uint64_t *d_sym, const uint32_t *d_entity,
+                       uint32_t n_traces, uint32_t n_entities, uint64_t *d_poff, uint64_t *d_psym, uint32_t *d_psrc,
+                       void *stream);
+/* Host pointers, synchronous, built on the _dev form (historystorage.go:50-51, naive.go:235-257,
+ * visualize.go:62-136): upload + project + download. poff[n_traces * n_entities + 1]; psym and psrc receive
+ * poff[n_traces * n_entities] elements (the elements whose id is not NMZ_NONE). */
+int nmz_po_project(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity, uint32_t n_traces,
+                   uint32_t n_entities, uint64_t *poff, uint64_t *psym, uint32_t *psrc);
+/* One pair on the calling host thread, no device work (historystorage.go:50-51, naive.go:235-257,
+ * visualize.go:62-136): plain vectors per entity, nmz_ed_align_wide_host's DP per entity, lift, concatenate. It shares
+ * nothing with the kernels: the check of the device forms. ea[n] / eb[m] are the entities of a / b. */
+int nmz_ed_align_po_host(const uint64_t *a, const uint32_t *ea, uint64_t n, const uint64_t *b, const uint32_t *eb,
+                         uint64_t m, uint32_t n_entities, uint32_t band, uint32_t *dist,
+                         nmz_edit_op *ops /* [band] */);
+/* The plan owns a wide align plan for projections of up to max_len elements and the sub-pair scratch for max_pairs
+ * pairs per launch (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136): per pair and entity one pair of
+ * projected traces, its distance and `band` op slots. The plan serves one stream at a time (a launch on another
+ * stream waits for the one before); destroy waits for its launches. */
+typedef struct nmz_ed_align_po_plan nmz_ed_align_po_plan;
+int nmz_ed_align_po_plan_create(nmz_ctx *ctx, uint32_t band, uint32_t n_entities, uint64_t max_len,
+                                uint64_t max_pairs, nmz_ed_align_po_plan **out);
+int nmz_ed_align_po_plan_destroy(nmz_ed_align_po_plan *plan);
+/* The plan's constants (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136): the inner plan's pairs in
+ * flight and history bytes, and the bytes of sub-pair scratch; each pointer may be NULL. */
+int nmz_ed_align_po_plan_info(const nmz_ed_align_po_plan *plan, uint32_t *slots, uint64_t *history_bytes,
+                              uint64_t *sub_pair_bytes);
+/* The original offsets, nmz_po_project_dev's outputs and device pairs in, d_dist[n_pairs] and d_ops[n_pairs * band]
+ * out (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136); enqueued on `stream` (NULL = the context's):
+ * the sub-pairs, the aligner over them and the gather, nothing else. n_pairs > max_pairs is NMZ_EINVAL. A pair with a
+ * projection longer than the plan's max_len gets dist = NMZ_NONE and sentinel ops. */
+int nmz_ed_align_po_pairs_dev(nmz_ed_align_po_plan *plan, const uint64_t *d_off, const uint64_t *d_poff,
+                              const uint64_t *d_psym, const uint32_t *d_psrc, const uint32_t *d_pairs,
+                              uint64_t n_pairs, uint32_t *d_dist, nmz_edit_op *d_ops /* [n_pairs * band] */,
+                              void *stream);
+/* Host pointers, synchronous, built on the _dev forms (historystorage.go:50-51, naive.go:235-257,
+ * visualize.go:62-136): upload + project + a plan for the longest projection among the pairs' traces + launches +
+ * download. The sub-pair scratch is capped at 256 MiB, so the pairs run in batches of max(1, 256 MiB / (n_entities *
+ * band * 12)) on one stream; the results do not depend on the batch size. */
+int nmz_ed_align_po_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
+                          uint32_t n_traces, uint32_t n_entities, const uint32_t *pairs, uint64_t n_pairs,
+                          uint32_t band, uint32_t *dist, nmz_edit_op *ops);
+/* From the traces to the PO profile (historystorage.go:50-51, naive.go:199-213, 235-257, visualize.go:62-136):
+ * project, the PO scripts, then k_script_moves_wide accumulating over the batches; the ops never leave the device.
+ * The result is byte-identical to nmz_move_profile_wide over nmz_ed_align_po_pairs' output. */
+int nmz_ed_diff_profile_po(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
+                           uint32_t n_traces, uint32_t n_entities, const uint32_t *pairs, uint64_t n_pairs,
+                           uint32_t band, const uint64_t *usym, uint64_t n_usym, uint32_t *dist /* may be NULL */,
+                           nmz_move_counts *counts, nmz_move_info *info);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(MW_THREADS) void k_script_moves_wide(const MvArgs g
 }
 
 // K9w's launch behind its argument checks and the clear; a band <= 64 goes to K9. The caller holds the context.
-static int moves_wide_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate) {
+int moves_wide_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate) {
     NMZ_TRY(aw_band(a.band));
     if (a.band <= NMZ_ALIGN_MAX_BAND) return moves_enqueue(ctx, st, a, accumulate);
     NMZ_CHECK(a.n_pairs * (uint64_t)a.band < (1ull << 32) && (a.band == 0 || a.n_pairs < (1ull << 32)),

@@ -1,7 +1,8 @@
 // K3 (edit distance) declarations shared by its translation units: the plan, the kernels' argument structs and the
 // entry points of ed_build.hip (plan builders), ed_tp.hip (two-phase search), ed_bv.hip and ed_wide.hip (kernels).
 // ed.hip holds k_ed_tile, the generic kernel, the k-NN list kernels, the search's dispatch and the C ABI. Also here:
-// what ed_moves_wide.hip (K9w) takes from ed_align_wide.hip (K8w's host helpers) and shares with ed_moves.hip (K9).
+// what ed_moves_wide.hip (K9w) takes from ed_align_wide.hip (K8w's host helpers) and shares with ed_moves.hip (K9),
+// and what ed_po.hip (K10) takes from both.
 #pragma once
 #include <memory>
 #include <string>
@@ -225,6 +226,8 @@ int moves_profile_host(MvBandCheck band_ok, MvAlignValidate validate, const uint
                        nmz_move_counts *counts, nmz_move_info *info);
 // K9's launch (band <= 64) behind its argument checks and the clear; the caller holds the context
 int moves_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate);
+// K9w's launch (every band 0 .. 1,024; ed_moves_wide.hip), for ed_po.hip; the caller holds the context
+int moves_wide_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate);
 
 }  // namespace nmz
 

@@ -108,7 +108,8 @@ struct HostPin {
     X(SLOT_DELIVERY_CLASSES) /* delivery_classes_locked: signatures and best gaps */                                  \
     X(SLOT_CONTRAST_RUN)     /* contrast_run: the run order, the merged list, the per-workgroup lists */              \
     /* nmz_order_contrast and nmz_order_contrast_runs: host forms, one synchronous call each */                       \
-    X(SLOT_CONTRAST_HOST)
+    X(SLOT_CONTRAST_HOST)                                                                                             \
+    X(SLOT_PO_SCAN)          /* po_project_enqueue: the temporary of the offsets' scan */
 enum Slot : int {
 #define X(name) name,
     NMZ_SLOTS(X)

@@ -235,13 +235,30 @@ class Naive(HistoryStorage):
     def AllPairsKNN(self, k, band):
         return allpairs_knn(self.load_all(), k, band)
 
-    def DiffSimilar(self, trace, k, band):
+    def DiffSimilar(self, trace, k, band, po=False):
         """SearchSimilar, then what differs: [(id, distance, script)] for the neighbours within the band, script the
         ops (EDIT_OP_DTYPE rows) that turn the stored run `id` into `trace` -- one edit_scripts call for all of them
         (edit_scripts_wide for 64 < band <= 1024). script_moves(stored, trace, script) names the events delivered
-        earlier or later."""
+        earlier or later. po=True: the neighbours still come from the exact SearchSimilar at `band`, but distance and
+        script are the per-entity ones (edit_scripts_po: interleavings of independent entities vanish); a neighbour
+        whose ED^PO exceeds the band is left out. `trace` must then be a SingleTrace carrying entities."""
         t = trace.symbols if isinstance(trace, SingleTrace) else np.asarray(trace, np.uint64)
         near = [(i, d) for i, d in self.SearchSimilar(trace, k, band) if d <= band]
+        if po:
+            if not isinstance(trace, SingleTrace):
+                raise TypeError("DiffSimilar(po=True) needs a SingleTrace carrying entities")
+            if not near:
+                return []
+            runs = []
+            for i, _ in near:
+                r, err = self.GetStoredHistory(i)
+                if err is not None:
+                    raise RuntimeError(f"failed to get history {i}: {err}")
+                runs.append(r)
+            ts, ent, names = po_entities(runs + [trace])
+            pairs = np.array([[r, len(near)] for r in range(len(near))], np.uint32)
+            es = edit_scripts_po(ts, ent, pairs, band, n_entities=max(len(names), 1), ctx=self._index.ctx)
+            return [(i, int(es.dist[r]), es.script(r).copy()) for r, (i, _) in enumerate(near) if es.dist[r] <= band]
         if not near:
             return []
         ts = TraceSet([self._index.ts.trace(i) for i, _ in near] + [t])
@@ -250,7 +267,7 @@ class Naive(HistoryStorage):
         es = align(ts, pairs, band, ctx=self._index.ctx)
         return [(i, d, es.script(r).copy()) for r, (i, d) in enumerate(near)]
 
-    def DiffFailing(self, band, k=1, ctx=None):
+    def DiffFailing(self, band, k=1, ctx=None, po=False):
         """Which events are delivered later, earlier, dropped or extra in this storage's failing runs, each measured
         against its k nearest passing runs (move_profile; move_profile_wide for 64 < band <= 1024). The runs are
         loaded and labelled as OrderContrast does it (IsSuccessful, naive.go:199-213; a run whose result cannot be
@@ -258,7 +275,9 @@ class Naive(HistoryStorage):
         SimilarityIndex over the passing runs answers the failing runs' queries; the pairs are (a = passing
         neighbour, b = failing run) for the neighbours within the band, so "later" reads "delivered later in the
         failing run". Returns the MoveProfile of one move_profile call, its .pairs the stored-run ids behind the
-        pairs; .top(k) ranks the symbols."""
+        pairs; .top(k) ranks the symbols. po=True: the neighbours still come from the exact search at `band`, the
+        scripts and the profile are the per-entity ones (move_profile_po), so events of independent entities that
+        merely interleaved differently are not counted; pairs with ED^PO > band count as beyond."""
         passing, failing = [], []
         for i in range(self.NrStoredHistories()):
             ok, err = self.IsSuccessful(i)
@@ -267,22 +286,26 @@ class Naive(HistoryStorage):
             t, err = self.GetStoredHistory(i)
             if err is not None:
                 raise RuntimeError(f"failed to get history {i}: {err}")  # naive.go:241 panics
-            (passing if ok else failing).append((i, t.symbols))
+            (passing if ok else failing).append((i, t))
         if not failing:
             raise ValueError("no failing run: nothing to contrast")
         if not passing:
             raise ValueError("no passing run: nothing to contrast")
-        index = SimilarityIndex(TraceSet([t for _, t in passing]), band, ctx=ctx)
+        index = SimilarityIndex(TraceSet([t.symbols for _, t in passing]), band, ctx=ctx)
         try:
-            ids, ds = index.query([t for _, t in failing], int(k))
+            ids, ds = index.query([t.symbols for _, t in failing], int(k))
         finally:
             index.close()
         near = [(int(j), f) for f in range(len(failing)) for j, d in zip(ids[f], ds[f])
                 if j != _lib.NMZ_NONE and d <= band]
-        ts = TraceSet([t for _, t in passing] + [t for _, t in failing])
         pairs = np.array([[j, len(passing) + f] for j, f in near], np.uint32).reshape(-1, 2)
-        profile = move_profile if band <= _lib.NMZ_ALIGN_MAX_BAND else move_profile_wide
-        prof = profile(ts, pairs, band, ctx=index.ctx)
+        if po:
+            ts, ent, names = po_entities([t for _, t in passing] + [t for _, t in failing])
+            prof = move_profile_po(ts, ent, pairs, band, ctx=index.ctx, n_entities=max(len(names), 1))
+        else:
+            ts = TraceSet([t.symbols for _, t in passing] + [t.symbols for _, t in failing])
+            profile = move_profile if band <= _lib.NMZ_ALIGN_MAX_BAND else move_profile_wide
+            prof = profile(ts, pairs, band, ctx=index.ctx)
         prof.pairs = np.array([[passing[j][0], failing[f][0]] for j, f in near], np.uint32).reshape(-1, 2)
         return prof
 
@@ -1004,3 +1027,175 @@ def move_profile_of_wide(ts, pairs, es, ctx=None, usym=None, want_partner=False,
         ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_WIDE_MAX_BAND else None)
         _lib.check(_lib.load().nmz_move_profile_wide(ctx.handle if ctx else None, *args))
     return MoveProfile(usym, counts, info[0], dist, partner)
+
+
+# ---- edit scripts and move profiles per entity: the partial-order view of a diff ---------------------------------
+def po_entities(traces):
+    """SingleTraces -> (TraceSet of event symbols, entity[N] uint32 parallel to its sym, names): ids global to the
+    set, assigned by sorted EntityID (names[id]), NMZ_NONE for an action without an event. Unlike po_inputs' ids
+    (dense per trace), equal ids in two traces mean the same entity: what the per-entity diff needs."""
+    ts = TraceSet([t.symbols for t in traces])
+    names = sorted({e for t in traces for e in t.entities if e is not None})
+    ids = {e: i for i, e in enumerate(names)}
+    ent = np.full(max(int(ts.off[-1]), 1), _lib.NMZ_NONE, np.uint32)
+    pos = 0
+    for t in traces:
+        for e in t.entities:
+            if e is not None:
+                ent[pos] = ids[e]
+            pos += 1
+    return ts, ent, names
+
+
+def _po_entity(n, entity, n_entities):
+    """entity[n] as a contiguous uint32 array, and n_entities (default: the largest id + 1, at least 1)."""
+    entity = np.ascontiguousarray(entity, np.uint32).reshape(-1)
+    if len(entity) < n:
+        raise ValueError(f"{len(entity)} entity ids for {n} elements")
+    if n_entities is None:
+        live = entity[:n][entity[:n] != _lib.NMZ_NONE]
+        n_entities = int(live.max()) + 1 if len(live) else 1
+    n_entities = int(n_entities)
+    if not 0 <= n_entities < 2**32:
+        raise ValueError(f"n_entities = {n_entities} does not fit uint32")
+    return entity, n_entities
+
+
+class PoProjection:
+    """po_project's result: poff[T * G + 1] (uint64), psym (uint64) and psrc (uint32): projected trace t * G + g is
+    psym[poff[t * G + g]:poff[t * G + g + 1]], and psrc holds each element's index in its trace."""
+
+    def __init__(self, poff, psym, psrc, n_entities):
+        self.poff = poff
+        self.psym = psym
+        self.psrc = psrc
+        self.n_entities = n_entities
+
+    def trace(self, t, g):
+        """(t|g, src_g(t)): the symbols of entity g in trace t, and their indices in t."""
+        lo, hi = int(self.poff[t * self.n_entities + g]), int(self.poff[t * self.n_entities + g + 1])
+        return self.psym[lo:hi], self.psrc[lo:hi]
+
+
+def po_project(ts, entity, n_entities=None, ctx=None):
+    """Every trace of ts split by entity on the device (nmz_po_project; DESIGN.md section 2, "Edit scripts per
+    entity"): a stable partition, elements with entity NMZ_NONE dropped. Returns a PoProjection."""
+    entity, G = _po_entity(int(ts.off[-1]), entity, n_entities)
+    T = len(ts)
+    kept = int((entity[:int(ts.off[-1])] != _lib.NMZ_NONE).sum())
+    poff = np.zeros(T * min(G, _lib.NMZ_PO_MAX_ENTITIES) + 1, np.uint64)
+    psym = np.zeros(max(kept, 1), np.uint64)
+    psrc = np.zeros(max(kept, 1), np.uint32)
+    ctx = ctx or (_lib.default_context() if T and 1 <= G <= _lib.NMZ_PO_MAX_ENTITIES else None)
+    _lib.check(_lib.load().nmz_po_project(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
+                                          _lib.ptr(entity), T, G, _lib.ptr(poff), _lib.ptr(psym), _lib.ptr(psrc)))
+    return PoProjection(poff, psym[:kept], psrc[:kept], G)
+
+
+def edit_scripts_po(ts, entity, pairs, band, n_entities=None, ctx=None):
+    """edit_scripts_wide per entity (nmz_ed_align_po_pairs): dist = min(sum over the entities of Lev(a|g, b|g),
+    band + 1) and, within the band, the entities' canonical scripts concatenated in ascending entity id with the
+    positions lifted back to the whole traces. dist == 0 <=> the traces are equal in partial order
+    (first_equal(..., po_reduction=True)). entity[N] is parallel to ts.sym, ids global to ts (po_entities). The same
+    EditScripts; with one entity and no NMZ_NONE, edit_scripts_wide's bytes."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = _move_band(band)
+    entity, G = _po_entity(int(ts.off[-1]), entity, n_entities)
+    dist = np.zeros(len(pairs), np.uint32)
+    ops = np.zeros((len(pairs), min(band, _lib.NMZ_ALIGN_WIDE_MAX_BAND)), _lib.EDIT_OP_DTYPE)
+    ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_WIDE_MAX_BAND
+                  and 1 <= G <= _lib.NMZ_PO_MAX_ENTITIES else None)
+    _lib.check(_lib.load().nmz_ed_align_po_pairs(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
+                                                 _lib.ptr(entity), len(ts), G, _lib.ptr(pairs), len(pairs), band,
+                                                 _lib.ptr(dist), _lib.ptr(ops) if ops.size else None))
+    return EditScripts(dist, ops, band)
+
+
+def edit_script_po_host(a, ea, b, eb, band, n_entities=None):
+    """One pair per entity on the host through nmz_ed_align_po_host (no GPU): (dist, script | None). Plain vectors
+    per entity and edit_script_wide_host's matrix per entity; the reference of edit_scripts_po."""
+    a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+    b = np.ascontiguousarray(b, np.uint64).reshape(-1)
+    band = _move_band(band)
+    ea, ga = _po_entity(len(a), ea, n_entities)
+    eb, gb = _po_entity(len(b), eb, n_entities)
+    dist = ctypes.c_uint32()
+    ops = np.zeros(min(band, _lib.NMZ_ALIGN_WIDE_MAX_BAND), _lib.EDIT_OP_DTYPE)
+    _lib.check(_lib.load().nmz_ed_align_po_host(_lib.ptr(a), _lib.ptr(ea), len(a), _lib.ptr(b), _lib.ptr(eb), len(b),
+                                                max(ga, gb), band, ctypes.byref(dist),
+                                                _lib.ptr(ops) if ops.size else None))
+    return dist.value, (ops[:dist.value] if dist.value <= band else None)
+
+
+def script_by_entity(ea, eb, ops):
+    """A PO script split into its segments: {entity id: the ops of that entity, in script order}. The entity of an
+    op is ea[a_pos] for a DEL or SUB and eb[b_pos] for an INS."""
+    out = {}
+    for o in ops:
+        g = int(eb[int(o["b_pos"])]) if int(o["kind"]) == _lib.NMZ_EDIT_INS else int(ea[int(o["a_pos"])])
+        out.setdefault(g, []).append(o)
+    return {g: np.array(v, _lib.EDIT_OP_DTYPE) for g, v in out.items()}
+
+
+class AlignPoPlan:
+    """A wide align plan for projections of up to max_len elements plus the sub-pair scratch for max_pairs pairs per
+    launch (nmz_ed_align_po_plan): pairs_dev makes the PO scripts of device pairs from nmz_po_project_dev's
+    outputs."""
+
+    def __init__(self, band, n_entities, max_len, max_pairs, ctx=None):
+        self.ctx = ctx or _lib.default_context()
+        self.band = int(band)
+        self.n_entities = int(n_entities)
+        self.plan = ctypes.c_void_p()
+        L = _lib.load()
+        _lib.check(L.nmz_ed_align_po_plan_create(self.ctx.handle, self.band, self.n_entities, int(max_len),
+                                                 int(max_pairs), ctypes.byref(self.plan)))
+        s, h, b = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(L.nmz_ed_align_po_plan_info(self.plan, ctypes.byref(s), ctypes.byref(h), ctypes.byref(b)))
+        self.slots, self.history_bytes, self.sub_pair_bytes = s.value, h.value, b.value
+
+    def project_dev(self, d_off, d_sym, d_entity, n_traces, d_poff, d_psym, d_psrc, stream=None):
+        """nmz_po_project_dev with the plan's n_entities: device pointers (ints), enqueued on `stream`."""
+        _lib.check(_lib.load().nmz_po_project_dev(
+            self.ctx.handle, ctypes.c_void_p(d_off), ctypes.c_void_p(d_sym), ctypes.c_void_p(d_entity), int(n_traces),
+            self.n_entities, ctypes.c_void_p(d_poff), ctypes.c_void_p(d_psym), ctypes.c_void_p(d_psrc),
+            ctypes.c_void_p(stream) if stream else None))
+
+    def pairs_dev(self, d_off, d_poff, d_psym, d_psrc, d_pairs, n_pairs, d_dist, d_ops, stream=None):
+        """Device pointers (ints): the original offsets, the projection, uint32 pairs[n_pairs][2] in; uint32
+        dist[n_pairs] and EDIT_OP_DTYPE ops[n_pairs][band] out, enqueued on `stream`. n_pairs <= max_pairs."""
+        _lib.check(_lib.load().nmz_ed_align_po_pairs_dev(
+            self.plan, ctypes.c_void_p(d_off), ctypes.c_void_p(d_poff), ctypes.c_void_p(d_psym),
+            ctypes.c_void_p(d_psrc), ctypes.c_void_p(d_pairs), int(n_pairs), ctypes.c_void_p(d_dist),
+            ctypes.c_void_p(d_ops), ctypes.c_void_p(stream) if stream else None))
+
+    def close(self):
+        if self.plan:
+            _lib.load().nmz_ed_align_po_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def move_profile_po(ts, entity, pairs, band, ctx=None, usym=None, n_entities=None):
+    """move_profile_wide over the per-entity scripts (nmz_ed_diff_profile_po): the traces are projected, the PO
+    scripts made as edit_scripts_po makes them and tallied on the device; the ops never come to the host. By
+    definition the profile that move_profile_of_wide gives for edit_scripts_po's output. The same MoveProfile."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    band = _move_band(band)
+    usym = _move_table(ts, usym)
+    entity, G = _po_entity(int(ts.off[-1]), entity, n_entities)
+    dist = np.zeros(len(pairs), np.uint32)
+    counts = np.zeros(len(usym), _lib.MOVE_COUNTS_DTYPE)
+    info = np.zeros(1, _lib.MOVE_INFO_DTYPE)
+    ctx = ctx or (_lib.default_context() if len(pairs) and band <= _lib.NMZ_ALIGN_WIDE_MAX_BAND
+                  and 1 <= G <= _lib.NMZ_PO_MAX_ENTITIES else None)
+    _lib.check(_lib.load().nmz_ed_diff_profile_po(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
+                                                  _lib.ptr(entity), len(ts), G, _lib.ptr(pairs), len(pairs), band,
+                                                  _lib.ptr(usym), len(usym), _lib.ptr(dist),
+                                                  _lib.ptr(counts) if len(usym) else None, _lib.ptr(info)))
+    return MoveProfile(usym, counts, info[0], dist)

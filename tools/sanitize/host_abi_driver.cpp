@@ -528,6 +528,43 @@ static void moves_cases() {
     CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
     CHECK(nmz_move_profile_wide_dev(nullptr, off2, both.data(), fwd, 1, 512, &d70, o70.data(), &x, 1, nullptr, &cx, &info,
                                     0, nullptr) == NMZ_EINVAL);
+    // per entity: everything in one entity gives the wide form's bytes; X and the block in two entities gives an
+    // empty script; then the refusals, each before the context
+    std::vector<uint32_t> e1(std::max(a.size(), b.size()), 0), ea(a.size()), eb(b.size()), eboth;
+    for (size_t i = 0; i < a.size(); ++i) ea[i] = a[i] == x ? 0 : 1;
+    for (size_t i = 0; i < b.size(); ++i) eb[i] = b[i] == x ? 0 : 1;
+    eboth.insert(eboth.end(), ea.begin(), ea.end());
+    eboth.insert(eboth.end(), eb.begin(), eb.end());
+    std::vector<nmz_edit_op> w70(70), q70(70);
+    uint32_t dq = 0;
+    CHECK(nmz_ed_align_wide_host(a.data(), a.size(), b.data(), b.size(), 70, &d70, w70.data()) == NMZ_OK && d70 == 64);
+    CHECK(nmz_ed_align_po_host(a.data(), e1.data(), a.size(), b.data(), e1.data(), b.size(), 1, 70, &dq, q70.data()) ==
+              NMZ_OK && dq == 64 && std::memcmp(w70.data(), q70.data(), 70 * sizeof(nmz_edit_op)) == 0);
+    CHECK(nmz_ed_align_po_host(a.data(), ea.data(), a.size(), b.data(), eb.data(), b.size(), 2, 70, &dq, q70.data()) ==
+              NMZ_OK && dq == 0 && q70[0].kind == NONE);
+    CHECK(nmz_ed_align_po_host(a.data(), ea.data(), a.size(), b.data(), eb.data(), b.size(), 1, 70, &dq, q70.data()) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ids are < n_entities (1) or NMZ_NONE") != nullptr);
+    CHECK(nmz_ed_align_po_host(a.data(), ea.data(), a.size(), b.data(), eb.data(), b.size(), 1025, 70, &dq,
+                               q70.data()) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "NMZ_PO_MAX_ENTITIES") != nullptr);
+    CHECK(nmz_ed_align_po_pairs(nullptr, off2, both.data(), eboth.data(), 2, 2, fwd, 1, 70, &dq, q70.data()) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    CHECK(nmz_ed_align_po_pairs(nullptr, off2, both.data(), eboth.data(), 2, 1, fwd, 1, 70, &dq, q70.data()) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "has entity id 1") != nullptr);
+    CHECK(nmz_ed_diff_profile_po(nullptr, off2, both.data(), eboth.data(), 2, 2, fwd, 1, 512, &x, 1, nullptr, &cx,
+                                 &info) == NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    std::vector<uint64_t> poff(2 * 2 + 1), psym(both.size());
+    std::vector<uint32_t> psrc(both.size());
+    CHECK(nmz_po_project(nullptr, off2, both.data(), eboth.data(), 2, 2, poff.data(), psym.data(), psrc.data()) ==
+          NMZ_EINVAL);
+    CHECK(std::strstr(nmz_last_error(), "ctx is NULL") != nullptr);
+    nmz_ed_align_po_plan *pp = nullptr;
+    CHECK(nmz_ed_align_po_plan_create(nullptr, 70, 2, 100, 0, &pp) == NMZ_EINVAL && pp == nullptr);
+    CHECK(std::strstr(nmz_last_error(), "max_pairs is 0") != nullptr);
 }
 
 // ScratchLayout (scratch_layout.h) over a host buffer that holds exactly the bytes asked for: under ASan a field
