@@ -1218,6 +1218,78 @@ int nmz_ed_diff_profile_po(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sy
                            uint32_t band, const uint64_t *usym, uint64_t n_usym, uint32_t *dist /* may be NULL */,
                            nmz_move_counts *counts, nmz_move_info *info);
 
+/* ---- PO k-NN search: the k nearest stored runs by per-entity edit distance ---------------------------------------
+ * The same build-defined extension (historystorage/historystorage.go:50-51; naive/naive.go:235-257;
+ * cli/tools/visualize.go:62-136): the search that goes with the per-entity scripts above. The store is a CSR off / sym
+ * with entity[N] exactly as nmz_ed_align_po_pairs takes them; the queries are a second CSR q_off / q_sym / q_entity
+ * over the same id space; q_self[Q] (uint32, optional) is the store index a query must skip, NMZ_NONE for none, NULL
+ * for none at all (queries = the store and q_self[i] = i: an all-pairs k-NN).
+ *   d(q, c) = ED^PO_band(query q, stored c) = min(sum over g of Lev(q|g, c|g), band + 1); d == 0 <=> tracesEqualInPO.
+ *   Result.   Per query the k smallest keys d << 32 | c over the stored c != q_self[q], ascending: (distance asc, id
+ *             asc), nmz_ed_plan_query_knn's order. Pairs beyond the band are listed at d = band + 1, smallest ids
+ *             first. Slots past the number of eligible stored traces hold NMZ_NONE / NMZ_NONE (UINT64_MAX as a key).
+ *             With n_entities == 1 and no NMZ_NONE the lists equal nmz_ed_plan_query_knn's over the same store.
+ *   Filter.   Every trace has a 256-byte profile of its projection: lenfold[b] (b < 32, uint32) = the sum of |t|g|
+ *             over g = b (mod 32), and gram[h] (h < 128, uint8 saturating at 255) = the number of positions p of any
+ *             t|g with mix(mix(prev + g) ^ cur) >> 57 == h, cur = t|g[p], prev = t|g[p - 1] or 0x9E3779B97F4A7C15 at
+ *             p == 0, mix the splitmix64 finaliser. LB_len = sum_b |lenfold_q[b] - lenfold_c[b]| and LB_gram =
+ *             ceil(sum_h |gram_q[h] - gram_c[h]| / 4) are lower bounds of sum_g Lev_g, so max(LB_len, LB_gram) > band
+ *             settles d = band + 1 exactly: the filter never changes a result.
+ * Limits, each NMZ_EINVAL with a message, checked before any device work (arguments before the context):
+ * band <= NMZ_PO_KNN_MAX_BAND; 1 <= k <= NMZ_PO_KNN_MAX_K; 1 <= n_entities <= NMZ_PO_MAX_ENTITIES; offsets starting at
+ * 0 and non-decreasing; traces shorter than 2^32 - 1; every id < n_entities or NMZ_NONE (the message names the element
+ * and whether it is a store or a query element); n_traces * n_entities < 2^31 - 1 and the same for the queries;
+ * q_self[i] < n_traces or NMZ_NONE. n_queries == 0 needs no device; n_traces == 0 gives all NMZ_NONE; band == 0 is the
+ * search for PO-equal runs. */
+#define NMZ_PO_KNN_MAX_BAND 64
+#define NMZ_PO_KNN_MAX_K 64
+#define NMZ_PO_KNN_OPT_NO_FILTER 1u /* every pair takes the DP path (A/B and tests); the lists do not change */
+#define NMZ_PO_KNN_OPT_WHOLE_BLOCKS 2u /* a block's survivors stay with one wave (A/B and tests); the same lists */
+#define NMZ_PO_KNN_NCOUNTERS 4
+/* Uploads the store, projects it, profiles it and keeps the projection and the profiles resident; sizes the
+ * query-side scratch of the _dev form for max_queries queries of max_query_elems elements in all
+ * (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136). Synchronous. The plan serves one stream at a time
+ * (a launch on another stream waits for the one before); destroy waits for its launches. */
+typedef struct nmz_po_knn_plan nmz_po_knn_plan;
+int nmz_po_knn_plan_create(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
+                           uint32_t n_traces, uint32_t n_entities, uint32_t band, uint64_t max_queries,
+                           uint64_t max_query_elems, uint32_t opts, nmz_po_knn_plan **out);
+int nmz_po_knn_plan_destroy(nmz_po_knn_plan *plan);
+/* The plan's resident bytes (projected store, profiles, query scratch) and the workgroups and waves of its latest
+ * search kernel launch (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136); each pointer may be NULL. */
+int nmz_po_knn_plan_info(const nmz_po_knn_plan *plan, uint64_t *resident_bytes, uint32_t *blocks, uint32_t *waves);
+/* Device pointers in, d_knn_keys[n_queries * k] (uint64 keys) out (historystorage.go:50-51, naive.go:235-257,
+ * visualize.go:62-136); enqueued on `stream` (NULL = the context's) and nothing else: the queries' projection and
+ * profiles, the search, the fill. n_queries > max_queries is NMZ_EINVAL (the message names both). The host cannot read
+ * d_q_off: offsets that do not start at 0, decrease or pass max_query_elems never leave the plan's scratch, the search
+ * then writes no list (every key stays UINT64_MAX) and nmz_po_knn_counters reports it. Query ids >= n_entities are
+ * dropped like NMZ_NONE; d_q_self may be NULL. n_queries == 0 enqueues nothing. */
+int nmz_po_knn_query_dev(nmz_po_knn_plan *plan, const uint64_t *d_q_off, const uint64_t *d_q_sym,
+                         const uint32_t *d_q_entity, const uint32_t *d_q_self, uint32_t n_queries, uint32_t k,
+                         uint64_t *d_knn_keys, void *stream);
+/* Host pointers, synchronous, every limit checked (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136):
+ * the queries run in batches of at most max_queries queries and max_query_elems elements on the context's stream; one
+ * query longer than max_query_elems is NMZ_EINVAL (the message names both). knn_id / knn_dist [n_queries * k]. */
+int nmz_po_knn_query(nmz_po_knn_plan *plan, const uint64_t *q_off, const uint64_t *q_sym, const uint32_t *q_entity,
+                     const uint32_t *q_self /* may be NULL */, uint32_t n_queries, uint32_t k, uint32_t *knn_id,
+                     uint32_t *knn_dist);
+/* One shot (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136): a plan for this store and these queries,
+ * the search, the plan's release; the buffers come from the context's pool. */
+int nmz_po_knn(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity, uint32_t n_traces,
+               uint32_t n_entities, const uint64_t *q_off, const uint64_t *q_sym, const uint32_t *q_entity,
+               const uint32_t *q_self /* may be NULL */, uint32_t n_queries, uint32_t band, uint32_t k,
+               uint32_t *knn_id, uint32_t *knn_dist);
+/* The latest search's work (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136), read after `stream`
+ * (NULL = the context's) has drained: out[0] pairs settled by the filter, out[1] pairs settled by the exact sum of the
+ * entities' length differences, out[2] pairs that ran a DP, out[3] pairs in band. Eligible pairs = out[0] + out[1] +
+ * out[2]. */
+int nmz_po_knn_counters(nmz_po_knn_plan *plan, uint64_t *out /* [NMZ_PO_KNN_NCOUNTERS] */, void *stream);
+/* The two lower bounds of one pair on the calling host thread, by the definition above, no device work
+ * (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136). It shares no table with the kernels: the check of
+ * the filter. */
+int nmz_po_knn_bound_host(const uint64_t *a, const uint32_t *ea, uint64_t n, const uint64_t *b, const uint32_t *eb,
+                          uint64_t m, uint32_t n_entities, uint32_t *lb_len, uint32_t *lb_gram);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

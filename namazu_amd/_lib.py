@@ -78,6 +78,9 @@ NMZ_EDIT_SUB, NMZ_EDIT_DEL, NMZ_EDIT_INS = 0, 1, 2
 NMZ_ALIGN_MAX_BAND = 64
 NMZ_ALIGN_WIDE_MAX_BAND = 1024  # the nmz_ed_align_wide_* entry points
 NMZ_PO_MAX_ENTITIES = 1024  # global entity ids of the per-entity (partial-order) edit scripts
+# the PO k-NN search (nmz_po_knn_*): its band and k limits, its option bit, its work counters
+NMZ_PO_KNN_MAX_BAND, NMZ_PO_KNN_MAX_K, NMZ_PO_KNN_NCOUNTERS = 64, 64, 4
+NMZ_PO_KNN_OPT_NO_FILTER, NMZ_PO_KNN_OPT_WHOLE_BLOCKS = 1, 2
 # move profiles: one table symbol's counters (nmz_move_counts) and the call's totals (nmz_move_info)
 MOVE_COUNTS_DTYPE = np.dtype([("later", "<u4"), ("earlier", "<u4"), ("dropped", "<u4"), ("extra", "<u4"),
                               ("sub_from", "<u4"), ("sub_to", "<u4"), ("n_pairs", "<u4"), ("reserved", "<u4"),
@@ -199,6 +202,14 @@ SIGNATURES = {
     "nmz_ed_align_po_pairs_dev": (_int, [_P, _P, _P, _P, _P, _P, _u64, _P, _P, _P]),
     "nmz_ed_align_po_pairs": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _u64, _u32, _P, _P]),
     "nmz_ed_diff_profile_po": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _u64, _u32, _P, _u64, _P, _P, _P]),
+    "nmz_po_knn_plan_create": (_int, [_P, _P, _P, _P, _u32, _u32, _u32, _u64, _u64, _u32, ctypes.POINTER(_P)]),
+    "nmz_po_knn_plan_destroy": (_int, [_P]),
+    "nmz_po_knn_plan_info": (_int, [_P, ctypes.POINTER(_u64), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "nmz_po_knn_query_dev": (_int, [_P, _P, _P, _P, _P, _u32, _u32, _P, _P]),
+    "nmz_po_knn_query": (_int, [_P, _P, _P, _P, _P, _u32, _u32, _P, _P]),
+    "nmz_po_knn": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _P, _P, _P, _u32, _u32, _u32, _P, _P]),
+    "nmz_po_knn_counters": (_int, [_P, _P, _P]),
+    "nmz_po_knn_bound_host": (_int, [_P, _P, _u64, _P, _P, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "nmz_replayable_delivery_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
     "nmz_replayable_delivery_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),
     "nmz_replayable_delivery_plan_destroy": (_int, [_P]),

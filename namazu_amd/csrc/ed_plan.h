@@ -2,7 +2,7 @@
 // entry points of ed_build.hip (plan builders), ed_tp.hip (two-phase search), ed_bv.hip and ed_wide.hip (kernels).
 // ed.hip holds k_ed_tile, the generic kernel, the k-NN list kernels, the search's dispatch and the C ABI. Also here:
 // what ed_moves_wide.hip (K9w) takes from ed_align_wide.hip (K8w's host helpers) and shares with ed_moves.hip (K9),
-// and what ed_po.hip (K10) takes from both.
+// what ed_po.hip (K10) takes from both, and what ed_po_knn.hip (K11) takes from ed_po.hip.
 #pragma once
 #include <memory>
 #include <string>
@@ -228,6 +228,12 @@ int moves_profile_host(MvBandCheck band_ok, MvAlignValidate validate, const uint
 int moves_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate);
 // K9w's launch (every band 0 .. 1,024; ed_moves_wide.hip), for ed_po.hip; the caller holds the context
 int moves_wide_enqueue(nmz_ctx *ctx, hipStream_t st, const MvArgs &a, int accumulate);
+
+
+// ---- the projection of ed_po.hip (K10a, the scan, K10b), for ed_po_knn.hip (K11); the caller holds the context ----
+int po_project_enqueue(nmz_ctx *ctx, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
+                       const uint32_t *d_ent, uint32_t n_traces, uint32_t G, uint64_t *d_poff, uint64_t *d_psym,
+                       uint32_t *d_psrc);
 
 }  // namespace nmz
 

@@ -251,9 +251,10 @@ static uint64_t po_max_len(const uint64_t *off, const uint32_t *entity, uint32_t
 }
 
 // K10a, the scan and K10b on `st`; the scan's temporary is the context's SLOT_PO_SCAN. The caller holds ctx.
-static int po_project_enqueue(nmz_ctx *ctx, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
-                              const uint32_t *d_ent, uint32_t n_traces, uint32_t G, uint64_t *d_poff, uint64_t *d_psym,
-                              uint32_t *d_psrc) {
+// (Also ed_po_knn.hip's projection of its store and of its queries: declared in ed_plan.h.)
+int po_project_enqueue(nmz_ctx *ctx, hipStream_t st, const uint64_t *d_off, const uint64_t *d_sym,
+                       const uint32_t *d_ent, uint32_t n_traces, uint32_t G, uint64_t *d_poff, uint64_t *d_psym,
+                       uint32_t *d_psrc) {
     NMZ_TRY(po_n_entities(G));
     NMZ_TRY(po_store(n_traces, G));
     NMZ_CHECK(d_poff != nullptr, "d_poff is NULL");

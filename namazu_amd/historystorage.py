@@ -235,18 +235,42 @@ class Naive(HistoryStorage):
     def AllPairsKNN(self, k, band):
         return allpairs_knn(self.load_all(), k, band)
 
-    def DiffSimilar(self, trace, k, band, po=False):
+    def SearchSimilarPO(self, trace, k, band):
+        """SearchSimilar under the per-entity distance: the k nearest stored traces to `trace` (a SingleTrace carrying
+        entities) by (ED^PO_band asc, id asc), as [(id, distance)]; a run that merely interleaved its independent
+        entities differently is at 0. The stored runs are projected once and stay on the GPU (PoSimilarityIndex)
+        until the storage holds a different number of traces. band <= 64 (the library refuses wider ones)."""
+        if not isinstance(trace, SingleTrace):
+            raise TypeError("SearchSimilarPO needs a SingleTrace carrying entities")
+        n = self.NrStoredHistories()
+        key = (band, n)
+        if getattr(self, "_po_index_key", None) != key:
+            if getattr(self, "_po_index", None) is not None:
+                self._po_index.close()
+                self._po_index = None
+            ts, ent, names = po_entities(self.traces())
+            self._po_index = PoSimilarityIndex(ts, ent, band, names)
+            self._po_index_key = key
+        ids, ds = self._po_index.query([trace], k)
+        return [(int(i), int(d)) for i, d in zip(ids[0], ds[0]) if i != _lib.NMZ_NONE]
+
+    def DiffSimilar(self, trace, k, band, po=False, po_search=False):
         """SearchSimilar, then what differs: [(id, distance, script)] for the neighbours within the band, script the
         ops (EDIT_OP_DTYPE rows) that turn the stored run `id` into `trace` -- one edit_scripts call for all of them
         (edit_scripts_wide for 64 < band <= 1024). script_moves(stored, trace, script) names the events delivered
         earlier or later. po=True: the neighbours still come from the exact SearchSimilar at `band`, but distance and
         script are the per-entity ones (edit_scripts_po: interleavings of independent entities vanish); a neighbour
-        whose ED^PO exceeds the band is left out. `trace` must then be a SingleTrace carrying entities."""
+        whose ED^PO exceeds the band is left out. `trace` must then be a SingleTrace carrying entities.
+        po_search=True (needs po=True, band <= 64): the neighbours come from SearchSimilarPO instead, so a run whose
+        exact distance exceeds the band is found when its ED^PO is within it."""
+        if po_search and not po:
+            raise ValueError("po_search=True needs po=True: the PO search goes with the per-entity scripts")
+        if po and not isinstance(trace, SingleTrace):
+            raise TypeError("DiffSimilar(po=True) needs a SingleTrace carrying entities")
         t = trace.symbols if isinstance(trace, SingleTrace) else np.asarray(trace, np.uint64)
-        near = [(i, d) for i, d in self.SearchSimilar(trace, k, band) if d <= band]
+        search = self.SearchSimilarPO if po_search else self.SearchSimilar
+        near = [(i, d) for i, d in search(trace, k, band) if d <= band]
         if po:
-            if not isinstance(trace, SingleTrace):
-                raise TypeError("DiffSimilar(po=True) needs a SingleTrace carrying entities")
             if not near:
                 return []
             runs = []
@@ -257,7 +281,8 @@ class Naive(HistoryStorage):
                 runs.append(r)
             ts, ent, names = po_entities(runs + [trace])
             pairs = np.array([[r, len(near)] for r in range(len(near))], np.uint32)
-            es = edit_scripts_po(ts, ent, pairs, band, n_entities=max(len(names), 1), ctx=self._index.ctx)
+            es = edit_scripts_po(ts, ent, pairs, band, n_entities=max(len(names), 1),
+                                 ctx=(self._po_index if po_search else self._index).ctx)
             return [(i, int(es.dist[r]), es.script(r).copy()) for r, (i, _) in enumerate(near) if es.dist[r] <= band]
         if not near:
             return []
@@ -267,7 +292,7 @@ class Naive(HistoryStorage):
         es = align(ts, pairs, band, ctx=self._index.ctx)
         return [(i, d, es.script(r).copy()) for r, (i, d) in enumerate(near)]
 
-    def DiffFailing(self, band, k=1, ctx=None, po=False):
+    def DiffFailing(self, band, k=1, ctx=None, po=False, po_search=False):
         """Which events are delivered later, earlier, dropped or extra in this storage's failing runs, each measured
         against its k nearest passing runs (move_profile; move_profile_wide for 64 < band <= 1024). The runs are
         loaded and labelled as OrderContrast does it (IsSuccessful, naive.go:199-213; a run whose result cannot be
@@ -277,7 +302,11 @@ class Naive(HistoryStorage):
         failing run". Returns the MoveProfile of one move_profile call, its .pairs the stored-run ids behind the
         pairs; .top(k) ranks the symbols. po=True: the neighbours still come from the exact search at `band`, the
         scripts and the profile are the per-entity ones (move_profile_po), so events of independent entities that
-        merely interleaved differently are not counted; pairs with ED^PO > band count as beyond."""
+        merely interleaved differently are not counted; pairs with ED^PO > band count as beyond. po_search=True
+        (needs po=True, band <= 64): a PoSimilarityIndex over the passing runs answers the failing runs' queries, so
+        the neighbours are the nearest passing runs by ED^PO, whatever their exact distance."""
+        if po_search and not po:
+            raise ValueError("po_search=True needs po=True: the PO search goes with the per-entity profile")
         passing, failing = [], []
         for i in range(self.NrStoredHistories()):
             ok, err = self.IsSuccessful(i)
@@ -291,9 +320,13 @@ class Naive(HistoryStorage):
             raise ValueError("no failing run: nothing to contrast")
         if not passing:
             raise ValueError("no passing run: nothing to contrast")
-        index = SimilarityIndex(TraceSet([t.symbols for _, t in passing]), band, ctx=ctx)
+        if po_search:
+            pts, pent, pnames = po_entities([t for _, t in passing])
+            index = PoSimilarityIndex(pts, pent, band, pnames, ctx=ctx)
+        else:
+            index = SimilarityIndex(TraceSet([t.symbols for _, t in passing]), band, ctx=ctx)
         try:
-            ids, ds = index.query([t.symbols for _, t in failing], int(k))
+            ids, ds = index.query([t if po_search else t.symbols for _, t in failing], int(k))
         finally:
             index.close()
         near = [(int(j), f) for f in range(len(failing)) for j, d in zip(ids[f], ds[f])
@@ -1199,3 +1232,151 @@ def move_profile_po(ts, entity, pairs, band, ctx=None, usym=None, n_entities=Non
                                                   _lib.ptr(usym), len(usym), _lib.ptr(dist),
                                                   _lib.ptr(counts) if len(usym) else None, _lib.ptr(info)))
     return MoveProfile(usym, counts, info[0], dist)
+
+
+# ---- PO k-NN search: the nearest stored runs by per-entity edit distance ---------------------------------------------
+def _po_knn_ctx(ctx, band, k, G, n_queries, n_traces):
+    """The context of a PO search: none where the library answers (or refuses) without a device."""
+    if ctx is not None:
+        return ctx
+    legal = (band <= _lib.NMZ_PO_KNN_MAX_BAND and 1 <= k <= _lib.NMZ_PO_KNN_MAX_K
+             and 1 <= G <= _lib.NMZ_PO_MAX_ENTITIES)
+    return _lib.default_context() if legal and n_queries and n_traces else None
+
+
+def po_knn(ts, entity, queries_ts, q_entity, k, band, n_entities=None, q_self=None, ctx=None):
+    """The k nearest traces of ts to every trace of queries_ts under ED^PO_band (nmz_po_knn; DESIGN.md section 2,
+    "PO k-NN search"): (ids [Q, k], dists [Q, k]) by (distance asc, id asc), pairs beyond the band at band + 1,
+    NMZ_NONE where fewer stored traces are eligible. entity / q_entity are parallel to ts.sym / queries_ts.sym, ids
+    global to both (po_entities). q_self[Q]: the store index each query skips (NMZ_NONE for none); queries = the
+    store with q_self = arange is the all-pairs k-NN. band <= 64, 1 <= k <= 64."""
+    band, k = int(band), int(k)
+    entity, G1 = _po_entity(int(ts.off[-1]), entity, n_entities)
+    q_entity, G2 = _po_entity(int(queries_ts.off[-1]), q_entity, n_entities)
+    G = max(G1, G2)
+    Q = len(queries_ts)
+    if q_self is not None:
+        q_self = np.ascontiguousarray(q_self, np.uint32).reshape(-1)
+        if len(q_self) < Q:
+            raise ValueError(f"{len(q_self)} q_self entries for {Q} queries")
+    shape = (Q, min(max(k, 0), _lib.NMZ_PO_KNN_MAX_K))
+    ids = np.full(shape, _lib.NMZ_NONE, np.uint32)
+    ds = np.full(shape, _lib.NMZ_NONE, np.uint32)
+    ctx = _po_knn_ctx(ctx, band, k, G, Q, len(ts))
+    _lib.check(_lib.load().nmz_po_knn(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
+                                      _lib.ptr(entity), len(ts), G, _lib.ptr(queries_ts.off),
+                                      _lib.ptr(queries_ts.sym), _lib.ptr(q_entity), _lib.ptr(q_self), Q, band, k,
+                                      _lib.ptr(ids), _lib.ptr(ds)))
+    return ids, ds
+
+
+def po_knn_bounds(a, ea, b, eb, n_entities=None):
+    """(LB_len, LB_gram) of one pair on the host (nmz_po_knn_bound_host): the two lower bounds of sum_g Lev(a|g, b|g)
+    that the search's filter uses, by their definition."""
+    a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+    b = np.ascontiguousarray(b, np.uint64).reshape(-1)
+    ea, ga = _po_entity(len(a), ea, n_entities)
+    eb, gb = _po_entity(len(b), eb, n_entities)
+    lb_len, lb_gram = ctypes.c_uint32(), ctypes.c_uint32()
+    _lib.check(_lib.load().nmz_po_knn_bound_host(_lib.ptr(a), _lib.ptr(ea), len(a), _lib.ptr(b), _lib.ptr(eb), len(b),
+                                                 max(ga, gb), ctypes.byref(lb_len), ctypes.byref(lb_gram)))
+    return lb_len.value, lb_gram.value
+
+
+class PoSimilarityIndex:
+    """A stored TraceSet with its entities, projected and profiled once and resident on the GPU for the PO search
+    (nmz_po_knn_plan). `names` are the store's entity names (po_entities): names[id]. A query's entities unknown to
+    the store all map to the one spare id len(names), and the plan is made with n_entities = len(names) + 1: exact,
+    since the store holds nothing there and each such element costs its one DEL whichever unknown entity it has."""
+
+    def __init__(self, ts, entity, band, names=(), ctx=None, max_queries=256, max_query_elems=1 << 18, opts=0,
+                 n_entities=None):
+        self.ts = ts
+        self.band = int(band)
+        self.names = list(names)
+        self._ids = {e: i for i, e in enumerate(self.names)}
+        # n_entities: for stores whose ids are numbers already (query_csr); the default leaves the spare id
+        self.n_entities = len(self.names) + 1 if n_entities is None else int(n_entities)
+        self.entity, _ = _po_entity(int(ts.off[-1]), entity, self.n_entities)
+        self.opts = int(opts)
+        self.max_queries = int(max_queries)
+        legal = self.band <= _lib.NMZ_PO_KNN_MAX_BAND and self.n_entities <= _lib.NMZ_PO_MAX_ENTITIES
+        self.ctx = ctx or (_lib.default_context() if legal else None)
+        self.plan = None
+        self._create(int(max_query_elems))
+
+    def _create(self, max_query_elems):
+        self.close()
+        plan = ctypes.c_void_p()
+        _lib.check(_lib.load().nmz_po_knn_plan_create(
+            self.ctx.handle if self.ctx else None, _lib.ptr(self.ts.off), _lib.ptr(self.ts.sym), _lib.ptr(self.entity),
+            len(self.ts), self.n_entities, self.band, self.max_queries, max_query_elems, self.opts, ctypes.byref(plan)))
+        self.plan = plan
+        self.max_query_elems = max_query_elems
+
+    def info(self):
+        """(resident bytes, workgroups, waves) of the plan and its latest search launch."""
+        b, g, w = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        _lib.check(_lib.load().nmz_po_knn_plan_info(self.plan, ctypes.byref(b), ctypes.byref(g), ctypes.byref(w)))
+        return b.value, g.value, w.value
+
+    def query_inputs(self, traces):
+        """SingleTraces -> (TraceSet, entity[N]) over the store's ids, unknown entities on the spare id."""
+        qts = TraceSet([t.symbols for t in traces])
+        ent = np.full(max(int(qts.off[-1]), 1), _lib.NMZ_NONE, np.uint32)
+        pos = 0
+        for t in traces:
+            for e in t.entities:
+                if e is not None:
+                    ent[pos] = self._ids.get(e, len(self.names))
+                pos += 1
+        return qts, ent
+
+    def query(self, traces, k, q_self=None):
+        """traces: SingleTraces carrying entities -> (ids [n, k], dists [n, k]) by (ED^PO_band asc, id asc)."""
+        qts, ent = self.query_inputs(traces)
+        return self.query_csr(qts, ent, k, q_self)
+
+    def query_csr(self, qts, q_entity, k, q_self=None):
+        """The same for a TraceSet and its entity ids (< n_entities or NMZ_NONE)."""
+        n, k = len(qts), int(k)
+        q_entity, _ = _po_entity(int(qts.off[-1]), q_entity, self.n_entities)
+        if q_self is not None:
+            q_self = np.ascontiguousarray(q_self, np.uint32).reshape(-1)
+            if len(q_self) < n:
+                raise ValueError(f"{len(q_self)} q_self entries for {n} queries")
+        longest = int(np.diff(qts.off).max()) if n else 0
+        if longest > self.max_query_elems:  # a plan whose scratch takes the longest query
+            self._create(2 * longest)
+        shape = (n, min(max(k, 0), _lib.NMZ_PO_KNN_MAX_K))
+        ids = np.full(shape, _lib.NMZ_NONE, np.uint32)
+        ds = np.full(shape, _lib.NMZ_NONE, np.uint32)
+        _lib.check(_lib.load().nmz_po_knn_query(self.plan, _lib.ptr(qts.off), _lib.ptr(qts.sym), _lib.ptr(q_entity),
+                                                _lib.ptr(q_self), n, k, _lib.ptr(ids), _lib.ptr(ds)))
+        return ids, ds
+
+    def query_dev(self, d_q_off, d_q_sym, d_q_entity, d_q_self, n_queries, k, d_knn_keys, stream=None):
+        """Device pointers (ints; d_q_self may be 0): uint64 keys dist << 32 | id into d_knn_keys[n_queries * k],
+        enqueued on `stream`. n_queries <= max_queries, the queries' elements <= max_query_elems."""
+        _lib.check(_lib.load().nmz_po_knn_query_dev(
+            self.plan, ctypes.c_void_p(d_q_off), ctypes.c_void_p(d_q_sym), ctypes.c_void_p(d_q_entity),
+            ctypes.c_void_p(d_q_self) if d_q_self else None, int(n_queries), int(k), ctypes.c_void_p(d_knn_keys),
+            ctypes.c_void_p(stream) if stream else None))
+
+    def counters(self, stream=None):
+        """The latest search's work: {filtered, length_sum, dp, in_band} pair counts."""
+        out = np.zeros(_lib.NMZ_PO_KNN_NCOUNTERS, np.uint64)
+        _lib.check(_lib.load().nmz_po_knn_counters(self.plan, _lib.ptr(out),
+                                                   ctypes.c_void_p(stream) if stream else None))
+        return dict(zip(("filtered", "length_sum", "dp", "in_band"), (int(v) for v in out)))
+
+    def close(self):
+        if self.plan:
+            _lib.load().nmz_po_knn_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
