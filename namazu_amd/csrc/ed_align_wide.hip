@@ -7,10 +7,10 @@
 // pair, sentinels behind the ops. The nmz_ed_align_wide_* entry points take every band 0 .. 1,024; a band <= 64 runs
 // k_ed_align through a narrow plan that the wide plan owns, so it gives the narrow entry points' bytes.
 //
-// k_ed_align_wide<C>: K8 one level up. One workgroup of 256 threads (4 waves) per pair,
-// grid-striding over the pairs; it owns one history slot of the plan. The band's 2w + 1 cells of a row (cell d <->
-// j = i + d - w) lie blocked over the threads, C in {1, 2, 3, 5, 9} consecutive cells per thread (w <= 127, 255,
-// 383, 639, 1,024), in named registers. Per row, ONE workgroup barrier:
+// k_ed_align_wide<C>: K8 one level up, over the same pieces (ed_align_dev.h). One
+// workgroup of 256 threads (4 waves) per pair, grid-striding over the pairs; it owns one history slot of the plan.
+// The band's 2w + 1 cells of a row (cell d <-> j = i + d - w) lie blocked over the threads, C in {1, 2, 3, 5, 9}
+// consecutive cells per thread (w <= 127, 255, 383, 639, 1,024), in named registers. Per row, ONE workgroup barrier:
 //   1. t[d] = min(prev[d] + (a[i-1] != b[j-1]), prev[d + 1] + 1). "Up" of a thread's last cell is the next
 //      thread's first: a DPP lane shift, and for lane 63 the next wave's first cell, which this wave worked out
 //      itself at the end of the row before (step 4). a and the row block's window of b are staged in LDS by
@@ -25,7 +25,7 @@
 //   The cut-off lags a row: a row's liveness travels with the next row's record, and a row without a cell <= w
 //   ends the pair at dist = w + 1 one row later (a dead row's successors are dead, and the last row needs no check:
 //   its own cell gives dist). The records are double-buffered by row parity, which one barrier per row makes safe.
-// The walk is K8's: the history a 64-row block at a time into LDS (the newest block is still there), LDS reads
+// The walk is K8's, written out here as there: the history a 64-row block at a time into LDS (the newest block is still there), LDS reads
 // only; every thread takes the same steps, thread 0 puts the t-th op found into slot dist - 1 - t of an LDS array
 // that was filled with sentinels, and one coalesced pass stores the pair's `band` slots. No scratch, no atomics;
 // nothing is allocated per launch.
@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "ed_align_dev.h"
 #include "ed_plan.h"
 #include "nmz_common.h"
 #include "nmz_internal.h"
@@ -41,10 +42,6 @@
 namespace nmz {
 
 constexpr uint32_t AW_THREADS = 256, AW_WAVES = 4;
-constexpr uint32_t AW_ROWS = 64;                   // rows per staged block
-constexpr int32_t AW_INF = 1 << 28;                // beyond any value a live row holds (<= 3 w + 1)
-constexpr uint64_t AW_MAX_LEN = 0xFFFFFFFFull;     // trace lengths 0 .. 2^32 - 2
-constexpr size_t AW_BUDGET = (size_t)256 << 20;    // the plan's history scratch, all slots together
 static_assert(NMZ_ALIGN_WIDE_MAX_BAND == 1024, "C = 9 cells per thread cover 2 * 1024 + 1 cells");
 
 // the widest band that C cells per thread hold: 2 w + 1 <= 256 C
@@ -57,9 +54,9 @@ static int aw_cells(uint32_t band) {
 // the workgroups a CU holds at once: registers give 8, 7, 6, 5 and 3 waves per SIMD, one
 // per workgroup; 160 KiB of LDS give 5 workgroups at C = 5 (31,896 bytes each) and 2 at C = 9 (54,440)
 static uint32_t aw_slots_per_cu(int C) { return C == 1 ? 8 : (C == 2 ? 7 : (C == 3 ? 6 : (C == 5 ? 5 : 2))); }
-static uint64_t aw_blocks(uint64_t max_len) { return std::max<uint64_t>(1, (max_len + AW_ROWS - 1) / AW_ROWS); }
+static uint64_t aw_blocks(uint64_t max_len) { return std::max<uint64_t>(1, (max_len + ALIGN_ROWS - 1) / ALIGN_ROWS); }
 // 64-bit words of one history block: [row][c][wave]{diag, low}
-static uint64_t aw_block_words(int C) { return (uint64_t)AW_ROWS * C * AW_WAVES * 2; }
+static uint64_t aw_block_words(int C) { return (uint64_t)ALIGN_ROWS * C * AW_WAVES * 2; }
 
 struct AwArgs {
     const uint64_t *off, *sym;
@@ -73,24 +70,6 @@ struct AwArgs {
     uint64_t slot_words;  // blocks * 64 * C * 4 * 2
 };
 
-// K8's cross-lane moves (ed_align.hip): DPP modifiers through the builtin. A lane without a source keeps `old`.
-constexpr int AW_ROW_SHR = 0x110, AW_ROW_BCAST15 = 0x142, AW_ROW_BCAST31 = 0x143;
-constexpr int AW_WAVE_SHL1 = 0x130, AW_WAVE_SHR1 = 0x138;  // lane i takes lane i + 1 / i - 1
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ int32_t aw_dpp(int32_t old, int32_t v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xF, false);
-}
-// inclusive minimum over lanes 0 .. lane of the wave
-__device__ __forceinline__ int32_t aw_scan_min(int32_t v) {
-    v = min(v, aw_dpp<AW_ROW_SHR + 1>(AW_INF, v));
-    v = min(v, aw_dpp<AW_ROW_SHR + 2>(AW_INF, v));
-    v = min(v, aw_dpp<AW_ROW_SHR + 4>(AW_INF, v));
-    v = min(v, aw_dpp<AW_ROW_SHR + 8>(AW_INF, v));
-    v = min(v, aw_dpp<AW_ROW_BCAST15, 0xA>(AW_INF, v));
-    v = min(v, aw_dpp<AW_ROW_BCAST31, 0xC>(AW_INF, v));
-    return v;
-}
-
 // what a wave tells the others in a row: double-buffered by the row's parity
 struct AwRec {
     int32_t wmin;  // min over the wave's cells of t[d] - d
@@ -102,20 +81,20 @@ struct AwRec {
 template <int C>
 __global__ __launch_bounds__(AW_THREADS) void k_ed_align_wide(const AwArgs g) {
     constexpr int WMAX = aw_wmax(C);
-    constexpr uint32_t BLK = AW_ROWS * C * AW_WAVES;  // ulonglong2 records of one history block
-    __shared__ uint64_t s_a[AW_ROWS];
-    __shared__ uint64_t s_b[AW_ROWS + 2 * WMAX];  // the forward pass; the walk keeps the pair's ops over it
+    constexpr uint32_t BLK = ALIGN_ROWS * C * AW_WAVES;  // ulonglong2 records of one history block
+    __shared__ uint64_t s_a[ALIGN_ROWS];
+    __shared__ uint64_t s_b[ALIGN_ROWS + 2 * WMAX];  // the forward pass; the walk keeps the pair's ops over it
     __shared__ ulonglong2 s_h[BLK];
     __shared__ AwRec s_rec[2][AW_WAVES + 1];      // [.][AW_WAVES]: "the wave after the last", never a cell
     __shared__ int32_t s_fin;
-    static_assert(sizeof(nmz_edit_op) * WMAX <= sizeof(uint64_t) * (AW_ROWS + 2 * WMAX), "the ops fit s_b");
+    static_assert(sizeof(nmz_edit_op) * WMAX <= sizeof(uint64_t) * (ALIGN_ROWS + 2 * WMAX), "the ops fit s_b");
     nmz_edit_op *s_ops = reinterpret_cast<nmz_edit_op *>(s_b);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int32_t w = (int32_t)g.band, W2 = 2 * w;
     const int32_t d0 = (int32_t)tid * C;             // this thread's first cell
     const int32_t dn = (int32_t)(wv + 1) * 64 * C;   // the next wave's first cell
     uint64_t *hist = g.hist + (uint64_t)blockIdx.x * g.slot_words;
-    if (tid < 2) s_rec[tid][AW_WAVES] = AwRec{AW_INF, -1, 0, 0};
+    if (tid < 2) s_rec[tid][AW_WAVES] = AwRec{ALIGN_INF, -1, 0, 0};
 
     for (uint64_t p = blockIdx.x; p < g.n_pairs; p += gridDim.x) {
         const uint32_t ia = g.pairs[2 * p], ib = g.pairs[2 * p + 1];
@@ -134,52 +113,28 @@ __global__ __launch_bounds__(AW_THREADS) void k_ed_align_wide(const AwArgs g) {
         } else {
             // ---- forward: row 0, then the rows in blocks of 64
             int32_t prev[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int32_t d = d0 + c;
-                const int64_t jv = (int64_t)d - w;
-                prev[c] = (d <= W2 && jv >= 0 && jv <= m) ? (int32_t)jv : AW_INF;
-            }
-            int32_t edge = (dn <= W2 && dn >= w && (int64_t)dn - w <= m) ? dn - w : AW_INF;  // row 0's cell dn
+            align_row0<C>(prev, d0, w, m);
+            int32_t edge = (dn <= W2 && dn >= w && (int64_t)dn - w <= m) ? dn - w : ALIGN_INF;  // row 0's cell dn
             bool alive = true, live_prev = true;
-            for (int64_t i0 = 0; i0 < n && alive; i0 += AW_ROWS) {
-                const int32_t rows = (int32_t)min((int64_t)AW_ROWS, n - i0);
-                __syncthreads();  // the previous block's reads of s_a / s_b / s_h; the previous pair's of s_ops
-                if (tid < AW_ROWS) s_a[tid] = i0 + tid < n ? a[i0 + tid] : 0;
-                for (int32_t t = (int32_t)tid; t < (int32_t)AW_ROWS + W2; t += AW_THREADS) {
-                    const int64_t jb = i0 - w + t;
-                    s_b[t] = (jb >= 0 && jb < m) ? b[jb] : 0;
-                }
-                __syncthreads();
+            for (int64_t i0 = 0; i0 < n && alive; i0 += ALIGN_ROWS) {
+                const int32_t rows = (int32_t)min((int64_t)ALIGN_ROWS, n - i0);
+                // its first barrier is also behind the previous block's reads of s_h and the previous pair's of s_ops;
+                // the unsigned stride keeps the 8, 7, 6, 5 and 3 waves per SIMD that aw_slots_per_cu counts on
+                align_stage<uint32_t, AW_THREADS>(s_a, s_b, a, n, b, m, i0, w, tid);
                 for (int32_t r = 1; r <= rows; ++r) {
-                    const int64_t i = i0 + r;
                     const int par = r & 1;
                     const uint64_t ai = s_a[r - 1];
-                    int32_t nxt = aw_dpp<AW_WAVE_SHL1>(AW_INF, prev[0]);  // cell d + 1 of the thread's last cell
+                    int32_t nxt = align_dpp<DPP_WAVE_SHL1>(ALIGN_INF, prev[0]);  // the next thread's first cell
                     nxt = lane == 63 ? edge : nxt;
-                    int32_t t[C], dg[C], up[C];
-                    bool valid[C], ne[C];
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const int32_t d = d0 + c;
-                        const int64_t jv = i + d - w;
-                        valid[c] = d <= W2 && jv >= 0 && jv <= m;
-                        const uint64_t bj = s_b[valid[c] ? r + d - 1 : 0];  // b[jv - 1]
-                        ne[c] = ai != bj;
-                        dg[c] = jv >= 1 ? prev[c] + (ne[c] ? 1 : 0) : AW_INF;
-                        up[c] = (c + 1 < C ? prev[c + 1 < C ? c + 1 : c] : nxt) + 1;
-                        t[c] = valid[c] ? min(dg[c], up[c]) : AW_INF;
-                    }
-                    // D[d] = d + min over d' <= d of (t[d'] - d')
-                    int32_t lp[C];
-                    lp[0] = t[0] - d0;
-#pragma unroll
-                    for (int c = 1; c < C; ++c) lp[c] = min(lp[c - 1], t[c] - (d0 + c));
-                    const int32_t incl = aw_scan_min(lp[C - 1]);
-                    const int32_t below = aw_dpp<AW_WAVE_SHR1>(AW_INF, incl);  // the lanes below, this wave
+                    int32_t t[C], lp[C];
+                    bool valid[C];
+                    AlignMoves<C> mv;
+                    align_row_candidates<C>(prev, nxt, ai, s_b, r, d0, w, m, i0 + r, t, valid, lp, mv);
+                    const int32_t incl = align_scan_min(lp[C - 1]);
+                    const int32_t below = align_dpp<DPP_WAVE_SHR1>(ALIGN_INF, incl);  // the lanes below, this wave
                     if (lane == 63) s_rec[par][wv].wmin = incl;
                     if (lane == 0) {
-                        s_rec[par][wv].t0 = valid[0] ? min(t[0], AW_INF) : -1;
+                        s_rec[par][wv].t0 = valid[0] ? min(t[0], ALIGN_INF) : -1;
                         s_rec[par][wv].live = live_prev ? 1 : 0;
                     }
                     __syncthreads();  // the row's one barrier
@@ -188,45 +143,34 @@ __global__ __launch_bounds__(AW_THREADS) void k_ed_align_wide(const AwArgs g) {
                         alive = false;
                         break;
                     }
-                    int32_t wbelow = AW_INF;  // the waves below this one
+                    int32_t wbelow = ALIGN_INF;  // the waves below this one
                     wbelow = wv > 0 ? min(wbelow, r0.wmin) : wbelow;
                     wbelow = wv > 1 ? min(wbelow, r1.wmin) : wbelow;
                     wbelow = wv > 2 ? min(wbelow, r2.wmin) : wbelow;
                     const int32_t own = wv == 0 ? r0.wmin : (wv == 1 ? r1.wmin : (wv == 2 ? r2.wmin : r3.wmin));
                     const int32_t nt0 = s_rec[par][wv + 1].t0;
-                    edge = nt0 < 0 ? AW_INF : min(min(nt0, dn + min(wbelow, own)), AW_INF);  // this row's cell dn
+                    edge = nt0 < 0 ? ALIGN_INF : min(min(nt0, dn + min(wbelow, own)), ALIGN_INF);  // this row's cell dn
                     const int32_t excl = min(below, wbelow);
-                    bool live = false;
+                    const bool live = align_row_close<C>(prev, valid, lp, excl, d0, w, mv);
 #pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const int32_t d = d0 + c;
-                        const int32_t cur = valid[c] ? min(d + min(excl, lp[c]), AW_INF) : AW_INF;
-                        const bool diag = valid[c] && dg[c] == cur && cur < AW_INF;
-                        const bool low = diag ? ne[c] : (valid[c] && up[c] == cur && cur < AW_INF);
-                        const uint64_t b1 = __ballot(diag), b0 = __ballot(low);
+                    for (int c = 0; c < C; ++c) {  // lane 0 puts the wave's words in the block's image
+                        const uint64_t b1 = __ballot(mv.diag[c]), b0 = __ballot(mv.low[c]);
                         if (lane == 0) s_h[((uint32_t)(r - 1) * C + c) * AW_WAVES + wv] = make_ulonglong2(b1, b0);
-                        live = live || cur <= w;
-                        prev[c] = cur;
                     }
                     live_prev = __ballot(live) != 0;
                 }
                 if (alive) {
                     __syncthreads();  // the block's image is whole
-                    ulonglong2 *hb = reinterpret_cast<ulonglong2 *>(hist) + (uint64_t)(i0 / AW_ROWS) * BLK;
+                    ulonglong2 *hb = reinterpret_cast<ulonglong2 *>(hist) + (uint64_t)(i0 / ALIGN_ROWS) * BLK;
                     for (uint32_t k = tid; k < (uint32_t)rows * C * AW_WAVES; k += AW_THREADS) hb[k] = s_h[k];
-                    loaded = i0 / AW_ROWS;
+                    loaded = i0 / ALIGN_ROWS;
                 }
             }
             if (!alive) {
                 dist = (uint32_t)w + 1;
             } else {
                 const int32_t df = (int32_t)(m - n) + w;  // in [0, 2 w] behind the length filter
-                if ((int32_t)tid == df / C) {
-                    int32_t v = prev[0];
-#pragma unroll
-                    for (int c = 1; c < C; ++c) v = (df % C) == c ? prev[c] : v;
-                    s_fin = v;
-                }
+                if ((int32_t)tid == df / C) s_fin = align_final_cell<C>(prev, df);
                 __syncthreads();
                 dist = (uint32_t)min(s_fin, w + 1);
             }
@@ -247,7 +191,7 @@ __global__ __launch_bounds__(AW_THREADS) void k_ed_align_wide(const AwArgs g) {
                     ka = (uint32_t)(i - 1), kb = 0, kk = NMZ_EDIT_DEL;
                     --i;
                 } else {
-                    const int64_t blk = (i - 1) / AW_ROWS;
+                    const int64_t blk = (i - 1) / ALIGN_ROWS;
                     if (blk != loaded) {
                         __syncthreads();
                         const ulonglong2 *hb = reinterpret_cast<const ulonglong2 *>(hist) + (uint64_t)blk * BLK;
@@ -257,7 +201,7 @@ __global__ __launch_bounds__(AW_THREADS) void k_ed_align_wide(const AwArgs g) {
                     }
                     const int64_t d = j - i + w;
                     if (d < 0 || d > W2) break;  // cannot happen on an optimal path of cost <= w
-                    const uint32_t r = (uint32_t)((i - 1) % AW_ROWS), c = (uint32_t)d % C, th = (uint32_t)d / C;
+                    const uint32_t r = (uint32_t)((i - 1) % ALIGN_ROWS), c = (uint32_t)d % C, th = (uint32_t)d / C;
                     const ulonglong2 h = s_h[(r * C + c) * AW_WAVES + (th >> 6)];
                     const uint32_t m1 = (uint32_t)(h.x >> (th & 63)) & 1u, m0 = (uint32_t)(h.y >> (th & 63)) & 1u;
                     if (m1) {
@@ -293,9 +237,7 @@ struct nmz_ed_align_wide_plan {
     uint64_t slot_words = 0;
     nmz_ed_align_plan *narrow = nullptr;  // band <= NMZ_ALIGN_MAX_BAND: k_ed_align's plan does the work
     nmz::DevBuf hist;
-    // the stream the plan's launches were enqueued on last, with an event after the latest one (destroy waits)
-    hipStream_t last = nullptr;
-    hipEvent_t ev = nullptr;
+    nmz::PlanFence fence;  // the slots serve one stream at a time (unused with a narrow plan, which has its own)
 };
 
 namespace nmz {
@@ -307,50 +249,25 @@ int aw_band(uint32_t band) {
     return NMZ_OK;
 }
 
-static int aw_len(const std::string &what, uint64_t len) {
-    NMZ_CHECK(len < AW_MAX_LEN, what + " has " + std::to_string(len) + " elements: at most 2^32 - 2");
-    return NMZ_OK;
-}
-
 // every limit of nmz_ed_align_wide_pairs, no device; *max_len = the longest trace of the pairs
 int aw_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs,
                 uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, uint64_t *max_len) {
-    NMZ_TRY(aw_band(band));
-    *max_len = 0;
-    if (n_pairs == 0) return NMZ_OK;
-    NMZ_CHECK(n_pairs <= (SIZE_MAX / sizeof(nmz_edit_op)) / NMZ_ALIGN_WIDE_MAX_BAND,
-              "n_pairs * band does not fit the output");
-    NMZ_CHECK(off && pairs && dist, "off, pairs or dist is NULL");
-    NMZ_CHECK(band == 0 || ops, "ops is NULL");
-    for (uint64_t t = 0; t < 2 * n_pairs; ++t)
-        NMZ_CHECK(pairs[t] < n_traces, "pair index out of range (pair " + std::to_string(t / 2) + ")");
-    for (uint32_t t = 0; t < n_traces; ++t) {
-        NMZ_CHECK(off[t] <= off[t + 1], "offsets must be non-decreasing (trace " + std::to_string(t) + ")");
-        NMZ_TRY(aw_len("trace " + std::to_string(t), off[t + 1] - off[t]));
-    }
-    for (uint64_t t = 0; t < 2 * n_pairs; ++t) *max_len = std::max(*max_len, off[pairs[t] + 1] - off[pairs[t]]);
-    NMZ_CHECK(off[n_traces] == off[0] || sym, "sym is NULL");
-    return NMZ_OK;
+    return align_validate_for(aw_band, NMZ_ALIGN_WIDE_MAX_BAND, off, sym, n_traces, pairs, n_pairs, band, dist, ops,
+                              max_len);
 }
 
 // the plan's shape for (band, max_len): no device. A band <= 64 has the narrow plan's shape.
 int aw_shape(uint32_t band, uint64_t max_len, uint64_t *slot_words) {
     NMZ_TRY(aw_band(band));
     if (band <= NMZ_ALIGN_MAX_BAND) return align_shape(band, max_len, slot_words);
-    NMZ_TRY(aw_len("a trace of max_len", max_len));
+    NMZ_TRY(align_len("a trace of max_len", max_len));
     *slot_words = aw_blocks(max_len) * aw_block_words(aw_cells(band));
-    NMZ_CHECK(*slot_words * 8 <= AW_BUDGET,
-              "max_len " + std::to_string(max_len) + ": one pair's history (" + std::to_string(*slot_words * 8) +
-                  " bytes) exceeds the plan's budget of " + std::to_string(AW_BUDGET) + " bytes");
-    return NMZ_OK;
+    return align_history_fits(max_len, *slot_words);
 }
 
 void aw_plan_destroy_locked(nmz_ed_align_wide_plan *p) {
     if (p->narrow) align_plan_destroy_locked(p->narrow);
-    if (p->ev) {
-        (void)hipEventSynchronize(p->ev);
-        (void)hipEventDestroy(p->ev);
-    }
+    p->fence.destroy();
     p->hist.release();
     delete p;
 }
@@ -369,13 +286,10 @@ int aw_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint64_t max_len, uint64_
     } else {
         p->slots = (uint32_t)std::max<uint64_t>(
             1, std::min<uint64_t>((uint64_t)std::max(ctx->n_cu, 1) * aw_slots_per_cu(aw_cells(band)),
-                                  AW_BUDGET / (slot_words * 8)));
+                                  ALIGN_BUDGET / (slot_words * 8)));
         p->hist.pool = &ctx->pool;
         rc = p->hist.ensure((size_t)p->slots * slot_words * 8);
-        if (rc == NMZ_OK && hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess) {
-            p->ev = nullptr;
-            rc = fail(NMZ_EHIP, "align wide plan: hipEventCreate failed");
-        }
+        if (rc == NMZ_OK) rc = p->fence.create("align wide plan");
     }
     if (rc != NMZ_OK) {
         aw_plan_destroy_locked(p);
@@ -392,7 +306,7 @@ int aw_enqueue(nmz_ed_align_wide_plan *p, hipStream_t st, const uint64_t *d_off,
               "n_pairs * band does not fit the output");
     if (n_pairs == 0) return NMZ_OK;
     NMZ_CHECK(d_off && d_pairs && d_dist && d_ops, "d_off, d_pairs, d_dist or d_ops is NULL");
-    if (p->last && p->last != st) NMZ_HIP(hipStreamWaitEvent(st, p->ev, 0));  // the slots serve one stream at a time
+    NMZ_TRY(p->fence.enter(st));
     AwArgs a{d_off, d_sym, d_pairs, n_pairs, p->band, p->max_len, d_dist, d_ops, p->hist.as<uint64_t>(), p->slot_words};
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_pairs, p->slots);
     int rc = NMZ_OK;
@@ -407,9 +321,37 @@ int aw_enqueue(nmz_ed_align_wide_plan *p, hipStream_t st, const uint64_t *d_off,
         }
         if (hipGetLastError() != hipSuccess) rc = fail(NMZ_EHIP, "k_ed_align_wide launch failed");
     }
-    p->last = st;
-    NMZ_HIP(hipEventRecord(p->ev, st));
+    NMZ_TRY(p->fence.leave(st));
     return rc;
+}
+
+// the host-arrays form behind nmz_ed_align_pairs and nmz_ed_align_wide_pairs, after their validation and shape
+int align_pairs_call(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                     uint64_t n_pairs, uint32_t band, uint64_t max_len, uint64_t slot_words, uint32_t *dist,
+                     nmz_edit_op *ops) {
+    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
+    CtxGuard g(ctx);
+    NMZ_TRY(g.rc);
+    HostCall call(ctx);
+    nmz_ed_align_wide_plan *plan = nullptr;
+    NMZ_TRY(aw_plan_create_locked(ctx, band, max_len, slot_words, &plan));
+    call.own_plan<aw_plan_destroy_locked>(plan);
+    hipStream_t st = ctx->stream;
+    const uint64_t total = off[n_traces];
+    const size_t n_ops = (size_t)n_pairs * band;
+    uint64_t *d_off, *d_sym;
+    uint32_t *d_pairs, *d_dist;
+    nmz_edit_op *d_ops;
+    ScratchLayout lay;
+    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_pairs, 2 * n_pairs).add(&d_dist, n_pairs);
+    lay.add(&d_ops, n_ops + 1);
+    NMZ_TRY(lay.bind(call.work));
+    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
+    NMZ_TRY(copy_h2d(d_pairs, pairs, 2 * n_pairs, st));
+    NMZ_TRY(aw_enqueue(plan, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops));
+    NMZ_TRY(copy_d2h(dist, d_dist, n_pairs, st));
+    NMZ_TRY(copy_d2h(ops, d_ops, n_ops, st));
+    return call.done();
 }
 
 }  // namespace nmz
@@ -418,67 +360,12 @@ using namespace nmz;
 
 extern "C" {
 
-// One pair on the calling thread (historystorage.go:50-51, naive.go:235-257, util/trace/trace.go:29-31):
-// nmz_ed_align_host's plan with 16-bit cells, which hold band + 1 <= 1,025. The +inf-banded matrix kept whole, row
-// by row (values capped at w + 1, which leaves every value <= w exact), then the walk by the definition. No ballots,
-// no closure scan, no packed history: nothing shared with the kernels.
+// One pair on the calling thread: the host aligner of ed_align.hip (align_host) with 16-bit cells, which hold
+// band + 1 <= 1,025.
 int nmz_ed_align_wide_host(const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m, uint32_t band, uint32_t *dist,
                            nmz_edit_op *ops) {
     NMZ_TRY(aw_band(band));
-    NMZ_TRY(aw_len("a", n));
-    NMZ_TRY(aw_len("b", m));
-    NMZ_CHECK((n == 0 || a) && (m == 0 || b), "a or b is NULL");
-    NMZ_CHECK(dist != nullptr, "dist is NULL");
-    NMZ_CHECK(band == 0 || ops, "ops is NULL");
-    for (uint32_t s = 0; s < band; ++s) ops[s] = nmz_edit_op{NMZ_NONE, NMZ_NONE, NMZ_NONE};
-    const int64_t w = band, W = 2 * w + 1, N = (int64_t)n, M = (int64_t)m;
-    const uint16_t cap = (uint16_t)(band + 1);
-    if ((n > m ? n - m : m - n) > band) {
-        *dist = band + 1;
-        return NMZ_OK;
-    }
-    std::vector<uint16_t> D;
-    try {
-        D.assign((size_t)(N + 1) * (size_t)W, cap);  // D[i][k]: the cell (i, j = i + k - w)
-    } catch (const std::exception &) {  // bad_alloc, or length_error past max_size()
-        return fail(NMZ_ENOMEM, "nmz_ed_align_wide_host: the band rows of " + std::to_string(n) + " x " +
-                                    std::to_string(W) + " 16-bit cells do not fit the host's memory");
-    }
-    auto at = [&](int64_t i, int64_t k) -> uint16_t & { return D[(size_t)i * (size_t)W + (size_t)k]; };
-    for (int64_t j = 0; j <= std::min(M, w); ++j) at(0, j + w) = (uint16_t)j;
-    for (int64_t i = 1; i <= N; ++i)
-        for (int64_t k = 0; k < W; ++k) {
-            const int64_t j = i + k - w;
-            if (j < 0 || j > M) continue;
-            int64_t v = cap;
-            if (j >= 1) v = std::min<int64_t>(v, at(i - 1, k) + (a[i - 1] != b[j - 1] ? 1 : 0));
-            if (k + 1 < W) v = std::min<int64_t>(v, at(i - 1, k + 1) + 1);
-            if (k >= 1 && j >= 1) v = std::min<int64_t>(v, at(i, k - 1) + 1);
-            at(i, k) = (uint16_t)v;
-        }
-    const uint32_t d = at(N, M - N + w);
-    *dist = d;
-    if (d > band) return NMZ_OK;
-    int64_t i = N, j = M;
-    uint32_t found = 0;
-    while ((i > 0 || j > 0) && found < d) {
-        const int64_t k = j - i + w;
-        const int64_t cur = at(i, k);
-        nmz_edit_op op{NMZ_NONE, NMZ_NONE, NMZ_NONE};
-        if (i > 0 && j > 0 && at(i - 1, k) + (a[i - 1] != b[j - 1] ? 1 : 0) == cur) {
-            if (a[i - 1] != b[j - 1]) op = nmz_edit_op{(uint32_t)(i - 1), (uint32_t)(j - 1), NMZ_EDIT_SUB};
-            --i, --j;
-        } else if (i > 0 && k + 1 < W && at(i - 1, k + 1) + 1 == cur) {
-            op = nmz_edit_op{(uint32_t)(i - 1), (uint32_t)j, NMZ_EDIT_DEL};
-            --i;
-        } else {
-            if (j == 0) return fail(NMZ_EINVAL, "nmz_ed_align_wide_host: the walk left the matrix");  // not reachable
-            op = nmz_edit_op{(uint32_t)i, (uint32_t)(j - 1), NMZ_EDIT_INS};
-            --j;
-        }
-        if (op.kind != NMZ_NONE) ops[d - 1 - found++] = op;
-    }
-    return NMZ_OK;
+    return align_host<uint16_t>("nmz_ed_align_wide_host", "16-bit cells", a, n, b, m, band, dist, ops);
 }
 
 int nmz_ed_align_wide_plan_create(nmz_ctx *ctx, uint32_t band, uint64_t max_len, nmz_ed_align_wide_plan **out) {
@@ -525,29 +412,7 @@ int nmz_ed_align_wide_pairs(nmz_ctx *ctx, const uint64_t *off, const uint64_t *s
     NMZ_TRY(aw_validate(off, sym, n_traces, pairs, n_pairs, band, dist, ops, &max_len));
     if (n_pairs == 0) return NMZ_OK;  // nothing to write: no device either
     NMZ_TRY(aw_shape(band, max_len, &slot_words));
-    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
-    CtxGuard g(ctx);
-    NMZ_TRY(g.rc);
-    HostCall call(ctx);
-    nmz_ed_align_wide_plan *plan = nullptr;
-    NMZ_TRY(aw_plan_create_locked(ctx, band, max_len, slot_words, &plan));
-    call.own_plan<aw_plan_destroy_locked>(plan);
-    hipStream_t st = ctx->stream;
-    const uint64_t total = off[n_traces];
-    const size_t n_ops = (size_t)n_pairs * band;
-    uint64_t *d_off, *d_sym;
-    uint32_t *d_pairs, *d_dist;
-    nmz_edit_op *d_ops;
-    ScratchLayout lay;
-    lay.add(&d_off, n_traces + 1).add(&d_sym, total + 1).add(&d_pairs, 2 * n_pairs).add(&d_dist, n_pairs);
-    lay.add(&d_ops, n_ops + 1);
-    NMZ_TRY(lay.bind(call.work));
-    NMZ_TRY(upload_csr(d_off, d_sym, off, sym, n_traces, st));
-    NMZ_TRY(copy_h2d(d_pairs, pairs, 2 * n_pairs, st));
-    NMZ_TRY(aw_enqueue(plan, st, d_off, d_sym, d_pairs, n_pairs, d_dist, d_ops));
-    NMZ_TRY(copy_d2h(dist, d_dist, n_pairs, st));
-    NMZ_TRY(copy_d2h(ops, d_ops, n_ops, st));
-    return call.done();
+    return align_pairs_call(ctx, off, sym, n_traces, pairs, n_pairs, band, max_len, slot_words, dist, ops);
 }
 
 }  // extern "C"

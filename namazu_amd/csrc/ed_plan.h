@@ -2,7 +2,8 @@
 // entry points of ed_build.hip (plan builders), ed_tp.hip (two-phase search), ed_bv.hip and ed_wide.hip (kernels).
 // ed.hip holds k_ed_tile, the generic kernel, the k-NN list kernels, the search's dispatch and the C ABI. Also here:
 // what ed_moves_wide.hip (K9w) takes from ed_align_wide.hip (K8w's host helpers) and shares with ed_moves.hip (K9),
-// what ed_po.hip (K10) takes from both, and what ed_po_knn.hip (K11) takes from ed_po.hip.
+// what ed_po.hip (K10) takes from both, and what ed_po_knn.hip (K11) takes from ed_po.hip. (The aligners' shared
+// device pieces are ed_align_dev.h; their shared host side and PlanFence are declared in nmz_internal.h.)
 #pragma once
 #include <memory>
 #include <string>

@@ -304,18 +304,13 @@ struct nmz_ed_align_po_plan {
     uint32_t *sub_pairs = nullptr, *sub_dist = nullptr;
     nmz_edit_op *sub_ops = nullptr;
     size_t sub_bytes = 0;
-    // the stream the plan's launches were enqueued on last, with an event after the latest one (destroy waits)
-    hipStream_t last = nullptr;
-    hipEvent_t ev = nullptr;
+    nmz::PlanFence fence;  // the sub-pair scratch serves one stream at a time
 };
 
 namespace nmz {
 
 static void po_plan_destroy_locked(nmz_ed_align_po_plan *p) {
-    if (p->ev) {
-        (void)hipEventSynchronize(p->ev);
-        (void)hipEventDestroy(p->ev);
-    }
+    p->fence.destroy();
     if (p->inner) aw_plan_destroy_locked(p->inner);
     p->sub.release();
     delete p;
@@ -347,10 +342,7 @@ static int po_plan_create_locked(nmz_ctx *ctx, uint32_t band, uint32_t G, uint64
         rc = lay.bind(p->sub);
         p->sub_bytes = lay.bytes();
     }
-    if (rc == NMZ_OK && hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess) {
-        p->ev = nullptr;
-        rc = fail(NMZ_EHIP, "align po plan: hipEventCreate failed");
-    }
+    if (rc == NMZ_OK) rc = p->fence.create("align po plan");
     if (rc != NMZ_OK) {
         po_plan_destroy_locked(p);
         return rc;
@@ -369,7 +361,7 @@ static int po_enqueue(nmz_ed_align_po_plan *p, hipStream_t st, const uint64_t *d
     NMZ_CHECK(d_off && d_poff && d_psym && d_psrc && d_pairs && d_dist,
               "d_off, d_poff, d_psym, d_psrc, d_pairs or d_dist is NULL");
     NMZ_CHECK(p->band == 0 || d_ops, "d_ops is NULL");
-    if (p->last && p->last != st) NMZ_HIP(hipStreamWaitEvent(st, p->ev, 0));  // the scratch serves one stream at a time
+    NMZ_TRY(p->fence.enter(st));
     const uint64_t subs = n_pairs * p->G;
     const unsigned cap = (unsigned)std::max(p->ctx->n_cu, 1) * PO_BLOCKS_PER_CU;
     hipLaunchKernelGGL(k_po_subpairs, dim3((unsigned)std::min<uint64_t>((subs + 255) / 256, cap)), dim3(256), 0, st,
@@ -383,8 +375,7 @@ static int po_enqueue(nmz_ed_align_po_plan *p, hipStream_t st, const uint64_t *d
         hipLaunchKernelGGL(k_po_gather, dim3((unsigned)std::min<uint64_t>(n_pairs, cap)), dim3(PO_THREADS), 0, st, a);
         if (hipGetLastError() != hipSuccess) rc = fail(NMZ_EHIP, "k_po_gather launch failed");
     }
-    p->last = st;
-    NMZ_HIP(hipEventRecord(p->ev, st));
+    NMZ_TRY(p->fence.leave(st));
     return rc;
 }
 

@@ -23,7 +23,7 @@
 //           v_sad_u8; max(LB_len, LB_gram) > w settles the pair at w + 1. One ballot gives the survivors.
 //   DP      the wave per surviving pair, distance only. The two rows of projected offsets 64 entities at a time:
 //           first the exact sum of ||q|g| - |c|g|| (> w: beyond, no DP), then for every entity where either side is
-//           not empty, ascending, K8's cell-form row step without history (ed_align.hip: 2w + 1 cells blocked over
+//           not empty, ascending, the cell-form row step without history (ed_align_dev.h: 2w + 1 cells blocked over
 //           the lanes, C in {1, 2, 3}, the DPP min-scan closure, q|g and the window of c|g staged in LDS per 64
 //           rows). Entity g runs against the budget r = w - (the sum so far): a row without a cell <= r, or a
 //           result > r, ends the pair at w + 1 (Lev_g > r => the sum > w: exact).
@@ -35,6 +35,7 @@
 #include <string>
 #include <vector>
 
+#include "ed_align_dev.h"
 #include "ed_knn_dev.h"
 #include "ed_plan.h"
 #include "nmz_common.h"
@@ -42,8 +43,6 @@
 
 namespace nmz {
 
-constexpr uint32_t PK_ROWS = 64;                 // rows per staged block
-constexpr int32_t PK_INF = 1 << 28;              // beyond any value a live row holds (<= 3 w + 1)
 constexpr uint32_t PK_WAVES_PER_CU = 12;         // persistent waves of k_po_knn: 3 per SIMD (144 .. 154 VGPRs)
 constexpr uint32_t PK_ITEMS_PER_WAVE = 4;        // the deal's aim: at least this many items per persistent wave
 constexpr uint32_t PK_PROF_BLOCKS_PER_CU = 16;   // k_po_knn_profile: one wave per workgroup
@@ -147,22 +146,6 @@ struct PkArgs {
     const uint32_t *over;              // the guard's flag
 };
 
-// Cross-lane moves of the row step as DPP modifiers, as ed_align.hip has them (a lane without a source keeps `old`)
-constexpr int PK_ROW_SHR = 0x110, PK_ROW_BCAST15 = 0x142, PK_ROW_BCAST31 = 0x143;
-constexpr int PK_WAVE_SHL1 = 0x130, PK_WAVE_SHR1 = 0x138;
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ int32_t pk_dpp(int32_t old, int32_t v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xF, false);
-}
-__device__ __forceinline__ int32_t pk_scan_min(int32_t v) {
-    v = min(v, pk_dpp<PK_ROW_SHR + 1>(PK_INF, v));
-    v = min(v, pk_dpp<PK_ROW_SHR + 2>(PK_INF, v));
-    v = min(v, pk_dpp<PK_ROW_SHR + 4>(PK_INF, v));
-    v = min(v, pk_dpp<PK_ROW_SHR + 8>(PK_INF, v));
-    v = min(v, pk_dpp<PK_ROW_BCAST15, 0xA>(PK_INF, v));
-    v = min(v, pk_dpp<PK_ROW_BCAST31, 0xC>(PK_INF, v));
-    return v;
-}
 __device__ __forceinline__ uint32_t pk_wave_sum(uint32_t v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -179,68 +162,32 @@ template <int C>
 __device__ __forceinline__ uint32_t pk_lev(const uint64_t *__restrict__ a, int64_t n, const uint64_t *__restrict__ b,
                                            int64_t m, int32_t w, int32_t r, uint64_t *s_a, uint64_t *s_b,
                                            uint32_t lane) {
-    const int32_t W2 = 2 * w;
+    const int32_t d0 = (int32_t)lane * C;  // this lane's first cell
     int32_t prev[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int32_t d = (int32_t)lane * C + c;
-        const int64_t jv = (int64_t)d - w;
-        prev[c] = (d <= W2 && jv >= 0 && jv <= m) ? (int32_t)jv : PK_INF;
-    }
-    for (int64_t i0 = 0; i0 < n; i0 += PK_ROWS) {
-        const int32_t rows = (int32_t)min((int64_t)PK_ROWS, n - i0);
-        __syncthreads();  // the previous block's reads of s_a / s_b
-        s_a[lane] = i0 + lane < n ? a[i0 + lane] : 0;
-        for (int32_t t = (int32_t)lane; t < (int32_t)PK_ROWS + W2; t += 64) {
-            const int64_t jb = i0 - w + t;
-            s_b[t] = (jb >= 0 && jb < m) ? b[jb] : 0;
-        }
-        __syncthreads();
+    AlignNoMoves distance_only;
+    align_row0<C>(prev, d0, w, m);
+    for (int64_t i0 = 0; i0 < n; i0 += ALIGN_ROWS) {
+        const int32_t rows = (int32_t)min((int64_t)ALIGN_ROWS, n - i0);
+        align_stage<int, 64>(s_a, s_b, a, n, b, m, i0, w, lane);
         for (int32_t rr = 1; rr <= rows; ++rr) {
-            const int64_t i = i0 + rr;
             const uint64_t ai = s_a[rr - 1];
-            const int32_t nxt = pk_dpp<PK_WAVE_SHL1>(PK_INF, prev[0]);  // cell d + 1 of the lane's last cell
-            int32_t t[C];
+            const int32_t nxt = align_dpp<DPP_WAVE_SHL1>(ALIGN_INF, prev[0]);  // the next lane's first cell
+            int32_t t[C], lp[C];
             bool valid[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int32_t d = (int32_t)lane * C + c;
-                const int64_t jv = i + d - w;
-                valid[c] = d <= W2 && jv >= 0 && jv <= m;
-                const uint64_t bj = s_b[valid[c] ? rr + d - 1 : 0];  // b[jv - 1]
-                const int32_t dg = jv >= 1 ? prev[c] + (ai != bj ? 1 : 0) : PK_INF;
-                const int32_t up = (c + 1 < C ? prev[c + 1 < C ? c + 1 : c] : nxt) + 1;
-                t[c] = valid[c] ? min(dg, up) : PK_INF;
-            }
-            // D[d] = d + min over d' <= d of (t[d'] - d')
-            int32_t lp[C];
-            lp[0] = t[0] - (int32_t)lane * C;
-#pragma unroll
-            for (int c = 1; c < C; ++c) lp[c] = min(lp[c - 1], t[c] - ((int32_t)lane * C + c));
-            const int32_t excl = pk_dpp<PK_WAVE_SHR1>(PK_INF, pk_scan_min(lp[C - 1]));  // lanes below this one
-            bool live = false;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int32_t d = (int32_t)lane * C + c;
-                const int32_t cur = valid[c] ? min(d + min(excl, lp[c]), PK_INF) : PK_INF;
-                live = live || cur <= r;
-                prev[c] = cur;
-            }
+            align_row_candidates<C>(prev, nxt, ai, s_b, rr, d0, w, m, i0 + rr, t, valid, lp, distance_only);
+            const int32_t excl = align_dpp<DPP_WAVE_SHR1>(ALIGN_INF, align_scan_min(lp[C - 1]));  // lanes below
+            const bool live = align_row_close<C>(prev, valid, lp, excl, d0, r, distance_only);
             if (__ballot(live) == 0) return (uint32_t)r + 1;  // the row's minimum has passed the budget
         }
     }
     const int32_t df = (int32_t)(m - n) + w;  // in [0, 2 w]
-    int32_t v = prev[0];
-#pragma unroll
-    for (int c = 1; c < C; ++c) v = (df % C) == c ? prev[c] : v;
-    v = __builtin_amdgcn_readlane(v, df / C);
-    return (uint32_t)min(v, r + 1);
+    return (uint32_t)min(__builtin_amdgcn_readlane(align_final_cell<C>(prev, df), df / C), r + 1);
 }
 
 template <int C>
 __global__ __launch_bounds__(64) void k_po_knn(const PkArgs g) {
-    __shared__ uint64_t s_a[PK_ROWS];
-    __shared__ uint64_t s_b[PK_ROWS + 2 * NMZ_PO_KNN_MAX_BAND];
+    __shared__ uint64_t s_a[ALIGN_ROWS];
+    __shared__ uint64_t s_b[ALIGN_ROWS + 2 * NMZ_PO_KNN_MAX_BAND];
     if (*g.over) return;
     const uint32_t lane = threadIdx.x;
     const uint32_t w = g.w, G = g.G;
@@ -441,8 +388,6 @@ static int pk_self(const uint32_t *q_self, uint32_t n_queries, uint32_t n_traces
     return NMZ_OK;
 }
 
-static int pk_cells(uint32_t band) { return band <= 31 ? 1 : (band <= 63 ? 2 : 3); }
-
 }  // namespace nmz
 
 struct nmz_po_knn_plan {
@@ -458,18 +403,13 @@ struct nmz_po_knn_plan {
     unsigned long long *next = nullptr;
     uint64_t resident_bytes = 0;
     uint32_t blocks = 0, waves = 0;  // of the latest k_po_knn launch
-    // the stream the plan's launches were enqueued on last, with an event after the latest one (destroy waits)
-    hipStream_t last = nullptr;
-    hipEvent_t ev = nullptr;
+    nmz::PlanFence fence;  // the query scratch serves one stream at a time
 };
 
 namespace nmz {
 
 static void pk_plan_destroy_locked(nmz_po_knn_plan *p) {
-    if (p->ev) {
-        (void)hipEventSynchronize(p->ev);
-        (void)hipEventDestroy(p->ev);
-    }
+    p->fence.destroy();
     p->store.release();
     p->query.release();
     delete p;
@@ -526,10 +466,7 @@ static int pk_plan_create_locked(nmz_ctx *ctx, const uint64_t *off, const uint64
         lq.add(&p->over, 1);
         NMZ_TRY(lq.bind(p->query));
         p->resident_bytes = ls.bytes() + lq.bytes();
-        if (hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess) {
-            p->ev = nullptr;
-            return fail(NMZ_EHIP, "po knn plan: hipEventCreate failed");
-        }
+        NMZ_TRY(p->fence.create("po knn plan"));
         NMZ_HIP(hipMemsetAsync(p->counters, 0, ED_CNT_WORDS * sizeof(uint64_t), st));
         NMZ_HIP(hipMemsetAsync(p->over, 0, sizeof(uint32_t), st));
         uint64_t *d_off, *d_sym;
@@ -567,7 +504,7 @@ static int pk_enqueue(nmz_po_knn_plan *p, hipStream_t st, const uint64_t *d_q_of
     if (n_queries == 0) return NMZ_OK;
     NMZ_CHECK(d_q_off && d_q_sym && d_q_ent && d_keys, "d_q_off, d_q_sym, d_q_entity or d_knn_keys is NULL");
     nmz_ctx *ctx = p->ctx;
-    if (p->last && p->last != st) NMZ_HIP(hipStreamWaitEvent(st, p->ev, 0));  // the scratch serves one stream at a time
+    NMZ_TRY(p->fence.enter(st));
     const uint32_t G = p->G, N = p->N;
     hipLaunchKernelGGL(k_po_knn_qoff, dim3(1), dim3(64), 0, st, d_q_off, n_queries, p->max_query_elems, p->q_safe,
                        p->over);
@@ -597,7 +534,7 @@ static int pk_enqueue(nmz_po_knn_plan *p, hipStream_t st, const uint64_t *d_q_of
         p->blocks = p->waves = blocks;  // the workgroup is the wave
         {
             KernelTimer kt(ctx, st, "po_knn");
-            switch (pk_cells(p->band)) {
+            switch (align_cells(p->band)) {
                 case 1: hipLaunchKernelGGL(k_po_knn<1>, dim3(blocks), dim3(64), 0, st, a); break;
                 case 2: hipLaunchKernelGGL(k_po_knn<2>, dim3(blocks), dim3(64), 0, st, a); break;
                 default: hipLaunchKernelGGL(k_po_knn<3>, dim3(blocks), dim3(64), 0, st, a); break;
@@ -611,8 +548,7 @@ static int pk_enqueue(nmz_po_knn_plan *p, hipStream_t st, const uint64_t *d_q_of
             if (hipGetLastError() != hipSuccess) rc = fail(NMZ_EHIP, "k_po_knn_fill launch failed");
         }
     }
-    p->last = st;
-    NMZ_HIP(hipEventRecord(p->ev, st));
+    NMZ_TRY(p->fence.leave(st));
     return rc;
 }
 

@@ -28,9 +28,62 @@ int match_validate(const uint64_t *sym, const int64_t *arrival, uint32_t E, cons
 int match_call(nmz_ctx *ctx, HostCall &call, const uint64_t *sym, const int64_t *arrival, uint32_t E,
                const uint64_t *run_off, const uint64_t *run_sym, uint64_t n_runs, uint32_t **d_pos);
 
-// ed_align.hip, for ed_moves.hip (nmz_move_profile, nmz_ed_diff_profile). align_validate: every limit of
-// nmz_ed_align_pairs, no device; *max_len = the longest trace of the pairs. align_shape: the plan's shape for
-// (band, max_len), no device. The _locked forms and align_enqueue want the caller to hold the context.
+// "This plan's scratch serves one stream at a time": the stream the plan's launches were enqueued on last, with an
+// event after the latest one. A launch on another stream first waits for that event; destroy waits for it on the host.
+// The messages of a failing call name it as the plans' own code did, hence `p`.
+struct PlanFence {
+    hipStream_t last = nullptr;
+    hipEvent_t ev = nullptr;
+    int create(const char *what) {  // what: the plan's name in the message
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) return NMZ_OK;
+        ev = nullptr;
+        return fail(NMZ_EHIP, std::string(what) + ": hipEventCreate failed");
+    }
+    int enter(hipStream_t st) {  // before the plan's launches on st
+        PlanFence *p = this;  // for the message's text
+        if (p->last && p->last != st) NMZ_HIP(hipStreamWaitEvent(st, p->ev, 0));
+        return NMZ_OK;
+    }
+    int leave(hipStream_t st) {  // behind them, whether or not they all went out
+        PlanFence *p = this;  // for the message's text
+        p->last = st;
+        NMZ_HIP(hipEventRecord(p->ev, st));
+        return NMZ_OK;
+    }
+    void destroy() {
+        if (!ev) return;
+        (void)hipEventSynchronize(ev);
+        (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+};
+
+// ed_align.hip: the host side that the aligners share, for ed_align_wide.hip (K8w), ed_moves.hip (nmz_move_profile,
+// nmz_ed_diff_profile) and ed_po.hip. The kernels' shared device side is ed_align_dev.h.
+// align_len: a trace length is 0 .. 2^32 - 2. align_history_fits: one pair's history against ALIGN_BUDGET, the
+// history scratch of a plan (all slots together).
+constexpr size_t ALIGN_BUDGET = (size_t)256 << 20;
+int align_len(const std::string &what, uint64_t len);
+int align_history_fits(uint64_t max_len, uint64_t slot_words);
+// The one validator body behind align_validate (band_ok = align_band, max_band = NMZ_ALIGN_MAX_BAND) and aw_validate
+// (aw_band, NMZ_ALIGN_WIDE_MAX_BAND; ed_plan.h): every limit of the *_pairs host forms, no device; *max_len = the
+// longest trace of the pairs.
+int align_validate_for(int (*band_ok)(uint32_t), uint32_t max_band, const uint64_t *off, const uint64_t *sym,
+                       uint32_t n_traces, const uint32_t *pairs, uint64_t n_pairs, uint32_t band, const uint32_t *dist,
+                       const nmz_edit_op *ops, uint64_t *max_len);
+// The one host aligner behind nmz_ed_align_host (Cell = uint8_t) and nmz_ed_align_wide_host (uint16_t), behind the
+// entry point's band check: a Cell holds band + 1. fn and cells ("cells", "16-bit cells") go into the messages.
+template <typename Cell>
+int align_host(const char *fn, const char *cells, const uint64_t *a, uint64_t n, const uint64_t *b, uint64_t m,
+               uint32_t band, uint32_t *dist, nmz_edit_op *ops);
+// ed_align_wide.hip: the host-arrays form behind nmz_ed_align_pairs and nmz_ed_align_wide_pairs, after the entry
+// point's validation and shape: a wide plan for the call (which owns a narrow one for a band <= 64), upload, enqueue,
+// download.
+int align_pairs_call(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
+                     uint64_t n_pairs, uint32_t band, uint64_t max_len, uint64_t slot_words, uint32_t *dist,
+                     nmz_edit_op *ops);
+// align_validate: every limit of nmz_ed_align_pairs. align_shape: the plan's shape for (band, max_len), no device.
+// The _locked forms and align_enqueue want the caller to hold the context.
 int align_band(uint32_t band);
 int align_validate(const uint64_t *off, const uint64_t *sym, uint32_t n_traces, const uint32_t *pairs,
                    uint64_t n_pairs, uint32_t band, const uint32_t *dist, const nmz_edit_op *ops, uint64_t *max_len);
