@@ -112,7 +112,11 @@ def family_counts(name):
 
 def expected_counters(name, w, self_excluded=True, no_filter=False):
     """The kernel's four counters for store = queries = the family at band w, from the host forms alone."""
-    D, LB, LS = family_counts(name)
+    return counters_from(*family_counts(name), w, self_excluded=self_excluded, no_filter=no_filter)
+
+
+def counters_from(D, LB, LS, w, self_excluded=True, no_filter=False):
+    """The same from any family's matrices (tests/test_po_many_host.py has a second one)."""
     elig = ~np.eye(len(D), dtype=bool) if self_excluded else np.ones(D.shape, bool)
     filt = elig & (LB > w) & (not no_filter)
     lens = elig & ~filt & (LS > w)
