@@ -100,9 +100,10 @@ def decide_events(seed, evhash, evclass, n_procs, rp, pp):
     return np.array(delays, np.int64), np.array(rows, ATTR_DTYPE) if rows else np.zeros(0, ATTR_DTYPE)
 
 
-def sweep(seed0, n_seeds, evhash, evclass, n_procs, target_slot, rp, pp, n_dump=0):
+def sweep(seed0, n_seeds, evhash, evclass, n_procs, target_slot, rp, pp, n_dump=0, hits=None):
     """-> (stats STATS_DTYPE[n_seeds], delays int64[n_dump, E], attrs ATTR_DTYPE[n_dump, sum n_procs],
-    outputs consumed [n_seeds, E])."""
+    outputs consumed [n_seeds, E]). hits, if given, is an int64[n_seeds, E] that receives the score of every event's
+    target slot (0 without a target)."""
     E = len(evhash)
     total = int(sum(int(n) for n in n_procs))
     stats = np.zeros(n_seeds, STATS_DTYPE)
@@ -122,6 +123,8 @@ def sweep(seed0, n_seeds, evhash, evclass, n_procs, target_slot, rp, pp, n_dump=
             t = NONE if target_slot is None else int(target_slot[e])
             if t != NONE:
                 ts += sc[t]
+                if hits is not None:
+                    hits[i, e] = sc[t]
             outs[i, e] = n_out
             if i < n_dump:
                 delays[i, e] = d

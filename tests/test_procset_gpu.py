@@ -200,6 +200,9 @@ def test_cross_path_equality(ctx, name):
     assert np.array_equal(d1, r.delays[2]) and np.array_equal(a1, r.attrs[2])
     dl, at = R.decide_events(p.Seed, EVHASH, EVCLASS, n_procs, rp, ref)
     assert np.array_equal(d1, dl) and same_attrs(a1, at)
+    # and the statistics of the same call: the sweep kernel's uniform form at prioritized = 64
+    st, _, _, _ = R.sweep(SEED0, 3, EVHASH, EVCLASS, n_procs, target, rp, ref)
+    assert same_stats(r.stats, st)
 
 
 def test_edge_cases(ctx):
