@@ -1290,6 +1290,37 @@ int nmz_po_knn_counters(nmz_po_knn_plan *plan, uint64_t *out /* [NMZ_PO_KNN_NCOU
 int nmz_po_knn_bound_host(const uint64_t *a, const uint32_t *ea, uint64_t n, const uint64_t *b, const uint32_t *eb,
                           uint64_t m, uint32_t n_entities, uint32_t *lb_len, uint32_t *lb_gram);
 
+/* ---- PO k-NN search over bands up to 1,024 ---------------------------------------------------------------------------
+ * The search above, word for word, with 0 <= band <= NMZ_PO_KNN_WIDE_MAX_BAND (historystorage/historystorage.go:50-51;
+ * naive/naive.go:235-257; cli/tools/visualize.go:62-136): the neighbours that go with nmz_ed_align_po_pairs' scripts
+ * at the bands real stores need. The plan type is the narrow form's, and nmz_po_knn_plan_destroy, _plan_info,
+ * _query_dev, _query and _counters serve a plan of either create. A band above 64 searches with k_po_knn_wide (four
+ * waves per pair; every entity's band clamped to min(what is left of the band, the longer projection), which is
+ * exact since Lev <= max(n, m)); a band <= 64 runs the narrow kernel and gives the narrow entry points' bytes and
+ * counters. The profiles, the two lower bounds and nmz_po_knn_bound_host do not depend on the band.
+ * Limits: band > NMZ_PO_KNN_WIDE_MAX_BAND is NMZ_EINVAL; every other limit, message and order of checks is the narrow
+ * form's. The narrow entry points keep NMZ_PO_KNN_MAX_BAND. */
+#define NMZ_PO_KNN_WIDE_MAX_BAND 1024
+#define NMZ_PO_KNN_WIDE_NCOUNTERS 9
+/* nmz_po_knn_wide_plan_create only: every entity laid out for the plan's band, not for its clamped one (A/B and
+ * tests); the lists do not change. Without effect at a band <= 64. */
+#define NMZ_PO_KNN_OPT_FULL_BAND 4u
+/* nmz_po_knn_plan_create for every band 0 .. 1,024 (historystorage.go:50-51, naive.go:235-257,
+ * visualize.go:62-136). */
+int nmz_po_knn_wide_plan_create(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
+                                uint32_t n_traces, uint32_t n_entities, uint32_t band, uint64_t max_queries,
+                                uint64_t max_query_elems, uint32_t opts, nmz_po_knn_plan **out);
+/* nmz_po_knn for every band 0 .. 1,024, one shot (historystorage.go:50-51, naive.go:235-257,
+ * visualize.go:62-136). */
+int nmz_po_knn_wide(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity, uint32_t n_traces,
+                    uint32_t n_entities, const uint64_t *q_off, const uint64_t *q_sym, const uint32_t *q_entity,
+                    const uint32_t *q_self /* may be NULL */, uint32_t n_queries, uint32_t band, uint32_t k,
+                    uint32_t *knn_id, uint32_t *knn_dist);
+/* nmz_po_knn_counters' four words, then out[4 .. 8]: the entity steps (one banded DP of one entity of one pair) that
+ * the latest search ran at 1, 2, 3, 5 and 9 cells per thread, i.e. at a clamped band <= 127, 255, 383, 639 and 1,024
+ * (historystorage.go:50-51, naive.go:235-257, visualize.go:62-136). All 0 for a plan whose band is <= 64. */
+int nmz_po_knn_wide_counters(nmz_po_knn_plan *plan, uint64_t *out /* [NMZ_PO_KNN_WIDE_NCOUNTERS] */, void *stream);
+
 /* ---- device groups: several GPUs behind one call (multi-GPU inside the C ABI) ----------------------------
  * The reference's callers are single processes (cli/run.go:123-136 initPolicy; cli/tools/visualize.go:138-172),
  * so one process must reach every GPU of a node. A group holds one context and one worker thread per device

@@ -81,6 +81,8 @@ NMZ_PO_MAX_ENTITIES = 1024  # global entity ids of the per-entity (partial-order
 # the PO k-NN search (nmz_po_knn_*): its band and k limits, its option bit, its work counters
 NMZ_PO_KNN_MAX_BAND, NMZ_PO_KNN_MAX_K, NMZ_PO_KNN_NCOUNTERS = 64, 64, 4
 NMZ_PO_KNN_OPT_NO_FILTER, NMZ_PO_KNN_OPT_WHOLE_BLOCKS = 1, 2
+# the same over bands up to 1,024 (nmz_po_knn_wide_*): its band limit, its nine counters, its own option bit
+NMZ_PO_KNN_WIDE_MAX_BAND, NMZ_PO_KNN_WIDE_NCOUNTERS, NMZ_PO_KNN_OPT_FULL_BAND = 1024, 9, 4
 # move profiles: one table symbol's counters (nmz_move_counts) and the call's totals (nmz_move_info)
 MOVE_COUNTS_DTYPE = np.dtype([("later", "<u4"), ("earlier", "<u4"), ("dropped", "<u4"), ("extra", "<u4"),
                               ("sub_from", "<u4"), ("sub_to", "<u4"), ("n_pairs", "<u4"), ("reserved", "<u4"),
@@ -209,6 +211,9 @@ SIGNATURES = {
     "nmz_po_knn_query": (_int, [_P, _P, _P, _P, _P, _u32, _u32, _P, _P]),
     "nmz_po_knn": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _P, _P, _P, _u32, _u32, _u32, _P, _P]),
     "nmz_po_knn_counters": (_int, [_P, _P, _P]),
+    "nmz_po_knn_wide_plan_create": (_int, [_P, _P, _P, _P, _u32, _u32, _u32, _u64, _u64, _u32, ctypes.POINTER(_P)]),
+    "nmz_po_knn_wide": (_int, [_P, _P, _P, _P, _u32, _u32, _P, _P, _P, _P, _u32, _u32, _u32, _P, _P]),
+    "nmz_po_knn_wide_counters": (_int, [_P, _P, _P]),
     "nmz_po_knn_bound_host": (_int, [_P, _P, _u64, _P, _P, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "nmz_replayable_delivery_host": (_int, [_P, _u32, _P, _P, _u32, _i64, _P, _P, _P, _P, _P, _P]),
     "nmz_replayable_delivery_plan_create": (_int, [_P, _P, _P, _u32, _i64, _P, _P, _P, _u64, ctypes.POINTER(_P)]),

@@ -1,5 +1,6 @@
 // The banded cell-form edit-distance row step, once: the device pieces that K8 (k_ed_align, ed_align.hip), K8w
-// (k_ed_align_wide, ed_align_wide.hip) and K11 (pk_lev of k_po_knn, ed_po_knn.hip) are built from.
+// (k_ed_align_wide, ed_align_wide.hip), K11 (pk_lev of k_po_knn, ed_po_knn.hip) and K11w (pkw_lev of k_po_knn_wide,
+// ed_po_knn_wide.hip) are built from.
 //
 // A pair (a, b) of n and m symbols under a band w: row i of the unit-cost matrix D keeps the 2w + 1 cells
 // d <-> j = i + d - w. A thread holds C consecutive cells d0 .. d0 + C - 1 in registers (prev[C]: the row above).
@@ -27,6 +28,27 @@ constexpr int32_t ALIGN_INF = 1 << 28;  // beyond any value a live row holds (<=
 
 // cells per lane of the one-wave forms (K8, K11) for a band <= 64
 inline int align_cells(uint32_t band) { return band <= 31 ? 1 : (band <= 63 ? 2 : 3); }
+
+// The four-wave forms (K8w, K11w): the band's cells blocked over a workgroup of 256 threads, C in {1, 2, 3, 5, 9}
+// consecutive cells per thread
+constexpr uint32_t AW_THREADS = 256, AW_WAVES = 4;
+// the widest band that C cells per thread hold: 2 w + 1 <= 256 C
+constexpr int aw_wmax(int C) {
+    return ((int)AW_THREADS * C - 1) / 2 < NMZ_ALIGN_WIDE_MAX_BAND ? ((int)AW_THREADS * C - 1) / 2
+                                                                   : NMZ_ALIGN_WIDE_MAX_BAND;
+}
+// cells per thread for a band
+__host__ __device__ inline int aw_cells(uint32_t band) {
+    const int w = (int)band;
+    return w <= aw_wmax(1) ? 1 : (w <= aw_wmax(2) ? 2 : (w <= aw_wmax(3) ? 3 : (w <= aw_wmax(5) ? 5 : 9)));
+}
+// what a wave tells the others in a row: double-buffered by the row's parity
+struct AwRec {
+    int32_t wmin;  // min over the wave's cells of t[d] - d
+    int32_t t0;    // t of the wave's first cell, -1 if the cell is outside the matrix
+    int32_t live;  // the row before had a cell <= the threshold in this wave
+    int32_t pad;
+};
 
 // Cross-lane moves of the row step as DPP modifiers (data-parallel primitives: no LDS round trip, unlike __shfl).
 // A lane without a source -- off the row's end, or in a row the mask leaves out -- keeps `old`.

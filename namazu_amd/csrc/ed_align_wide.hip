@@ -41,16 +41,9 @@
 
 namespace nmz {
 
-constexpr uint32_t AW_THREADS = 256, AW_WAVES = 4;
+// AW_THREADS, AW_WAVES, aw_wmax, aw_cells and AwRec: ed_align_dev.h, shared with K11w
 static_assert(NMZ_ALIGN_WIDE_MAX_BAND == 1024, "C = 9 cells per thread cover 2 * 1024 + 1 cells");
 
-// the widest band that C cells per thread hold: 2 w + 1 <= 256 C
-constexpr int aw_wmax(int C) { return std::min<int>(NMZ_ALIGN_WIDE_MAX_BAND, ((int)AW_THREADS * C - 1) / 2); }
-// cells per thread for a band
-static int aw_cells(uint32_t band) {
-    for (int C : {1, 2, 3, 5}) if ((int)band <= aw_wmax(C)) return C;
-    return 9;
-}
 // the workgroups a CU holds at once: registers give 8, 7, 6, 5 and 3 waves per SIMD, one
 // per workgroup; 160 KiB of LDS give 5 workgroups at C = 5 (31,896 bytes each) and 2 at C = 9 (54,440)
 static uint32_t aw_slots_per_cu(int C) { return C == 1 ? 8 : (C == 2 ? 7 : (C == 3 ? 6 : (C == 5 ? 5 : 2))); }
@@ -68,14 +61,6 @@ struct AwArgs {
     nmz_edit_op *ops;
     uint64_t *hist;       // [slots][slot_words]
     uint64_t slot_words;  // blocks * 64 * C * 4 * 2
-};
-
-// what a wave tells the others in a row: double-buffered by the row's parity
-struct AwRec {
-    int32_t wmin;  // min over the wave's cells of t[d] - d
-    int32_t t0;    // t of the wave's first cell, -1 if the cell is outside the matrix
-    int32_t live;  // the row before had a cell <= w in this wave
-    int32_t pad;
 };
 
 template <int C>

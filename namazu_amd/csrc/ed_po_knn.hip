@@ -31,6 +31,10 @@
 //           (w + 1, the smallest ids not listed and not q_self).
 // Counters, striped as the bit-parallel search keeps them: 0 pairs settled by the filter, 1 pairs settled by the
 // exact length sum, 2 pairs that ran a DP, 3 pairs in band. Plain vector stores and atomics on the lists only.
+//
+// Bands 65 .. 1,024 (the nmz_po_knn_wide_* entry points, at this file's end): the same plan, validators, batcher and
+// enqueue; pk_enqueue launches K11w (k_po_knn_wide, ed_po_knn_wide.hip) in K11b's place when the plan's band is
+// above 64. ed_po_knn.h holds what the two kernels share: the argument block, the filter, the counters' layout.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -38,16 +42,14 @@
 #include "ed_align_dev.h"
 #include "ed_knn_dev.h"
 #include "ed_plan.h"
+#include "ed_po_knn.h"
 #include "nmz_common.h"
 #include "nmz_internal.h"
 
 namespace nmz {
 
 constexpr uint32_t PK_WAVES_PER_CU = 12;         // persistent waves of k_po_knn: 3 per SIMD (144 .. 154 VGPRs)
-constexpr uint32_t PK_ITEMS_PER_WAVE = 4;        // the deal's aim: at least this many items per persistent wave
 constexpr uint32_t PK_PROF_BLOCKS_PER_CU = 16;   // k_po_knn_profile: one wave per workgroup
-constexpr uint32_t PK_PROF_WORDS = 64;           // 32 lenfold words + 128 gram bytes
-constexpr uint32_t PK_NCOUNTERS = 4;
 constexpr uint64_t PK_GRAM_START = 0x9E3779B97F4A7C15ull;
 static_assert(NMZ_PO_KNN_MAX_BAND == 64 && NMZ_PO_KNN_MAX_K == 64, "three cells per lane cover 2 * 64 + 1");
 
@@ -132,30 +134,7 @@ __global__ __launch_bounds__(64) void k_po_knn_profile(const uint64_t *__restric
 }
 
 // ---- K11b ----
-struct PkArgs {
-    const uint64_t *poff, *psym;  // the store, projected
-    const uint32_t *prof;
-    const uint64_t *q_poff, *q_psym;  // the queries, projected
-    const uint32_t *q_prof;
-    const uint32_t *q_self;  // may be NULL
-    uint32_t N, G, k, w, no_filter, NB, parts;
-    uint64_t n_items;  // n_queries * NB * parts
-    uint64_t *knn;
-    uint64_t *counters;                // [ED_CNT_WORDS]
-    unsigned long long *next;          // the item counter
-    const uint32_t *over;              // the guard's flag
-};
-
-__device__ __forceinline__ uint32_t pk_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint64_t pk_lane64(uint64_t v, int src) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src);
-    return ((uint64_t)hi << 32) | lo;
-}
+// PkArgs, pk_wave_sum, pk_lane64 and the filter (pk_filter_passes): ed_po_knn.h, shared with K11w
 
 // Lev(a, b) when it is <= r, anything > r otherwise; |n - m| <= r <= w. The band's cells are laid out for w.
 template <int C>
@@ -209,27 +188,8 @@ __global__ __launch_bounds__(64) void k_po_knn(const PkArgs g) {
             // ---- the filter: a lane per candidate
             const uint32_t *__restrict__ qp = g.q_prof + (uint64_t)q * PK_PROF_WORDS;  // uniform
             const uint4 *__restrict__ cp = (const uint4 *)(g.prof + (uint64_t)(valid ? cand : 0) * PK_PROF_WORDS);
-            uint64_t lb_len = 0;
-            uint32_t sad = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const uint4 c = cp[i];
-                const uint32_t a0 = qp[4 * i], a1 = qp[4 * i + 1], a2 = qp[4 * i + 2], a3 = qp[4 * i + 3];
-                lb_len += (c.x > a0 ? c.x - a0 : a0 - c.x);
-                lb_len += (c.y > a1 ? c.y - a1 : a1 - c.y);
-                lb_len += (c.z > a2 ? c.z - a2 : a2 - c.z);
-                lb_len += (c.w > a3 ? c.w - a3 : a3 - c.w);
-            }
-#pragma unroll
-            for (int i = 8; i < 16; ++i) {
-                const uint4 c = cp[i];
-                sad = __builtin_amdgcn_sad_u8(c.x, qp[4 * i], sad);
-                sad = __builtin_amdgcn_sad_u8(c.y, qp[4 * i + 1], sad);
-                sad = __builtin_amdgcn_sad_u8(c.z, qp[4 * i + 2], sad);
-                sad = __builtin_amdgcn_sad_u8(c.w, qp[4 * i + 3], sad);
-            }
-            const uint64_t lb_gram = (sad + 3) / 4;
-            survive = valid && (lb_len > lb_gram ? lb_len : lb_gram) <= w;
+            const bool passes = pk_filter_passes(qp, cp, w);  // every lane: no branch round the loads
+            survive = valid && passes;
         }
         uint64_t todo = __ballot(survive);
         if (part == 0) n_filter += (uint32_t)__popcll(__ballot(valid)) - (uint32_t)__popcll(todo);
@@ -337,6 +297,15 @@ static int pk_band(uint32_t band) {
     return NMZ_OK;
 }
 
+// the same for the wide entry points (K11w: 65 .. 1,024; a band <= 64 runs K11b)
+static int pkw_band(uint32_t band) {
+    NMZ_CHECK(band <= NMZ_PO_KNN_WIDE_MAX_BAND, "band " + std::to_string(band) +
+                                                    " exceeds NMZ_PO_KNN_WIDE_MAX_BAND (1024): the PO search over "
+                                                    "wider bands is not built yet");
+    return NMZ_OK;
+}
+typedef int (*PkBandCheck)(uint32_t band);
+
 static int pk_k(uint32_t k) {
     NMZ_CHECK(k >= 1 && k <= NMZ_PO_KNN_MAX_K, "k " + std::to_string(k) + " must be 1 .. NMZ_PO_KNN_MAX_K (64)");
     return NMZ_OK;
@@ -426,16 +395,18 @@ static int pk_profile_enqueue(nmz_ctx *ctx, hipStream_t st, const uint64_t *d_po
     return NMZ_OK;
 }
 
-// the plan's own limits, no device
-static int pk_plan_shape(uint32_t band, uint32_t G, uint64_t max_queries, uint32_t opts) {
-    NMZ_TRY(pk_band(band));
+// the plan's own limits, no device; known = the opts bits of the entry point
+static int pk_plan_shape(PkBandCheck band_ok, uint32_t known, uint32_t band, uint32_t G, uint64_t max_queries,
+                         uint32_t opts) {
+    NMZ_TRY(band_ok(band));
     NMZ_TRY(pk_entities(G));
     NMZ_CHECK(max_queries >= 1, "max_queries is 0");
     NMZ_TRY(pk_count("max_queries", max_queries, G));
-    NMZ_CHECK((opts & ~(uint32_t)(NMZ_PO_KNN_OPT_NO_FILTER | NMZ_PO_KNN_OPT_WHOLE_BLOCKS)) == 0,
-              "opts " + std::to_string(opts) + ": unknown bits");
+    NMZ_CHECK((opts & ~known) == 0, "opts " + std::to_string(opts) + ": unknown bits");
     return NMZ_OK;
 }
+constexpr uint32_t PK_OPTS = NMZ_PO_KNN_OPT_NO_FILTER | NMZ_PO_KNN_OPT_WHOLE_BLOCKS;
+constexpr uint32_t PKW_OPTS = PK_OPTS | NMZ_PO_KNN_OPT_FULL_BAND;
 
 // upload, project and profile the store, size the query scratch; the caller holds ctx and has validated
 static int pk_plan_create_locked(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
@@ -523,16 +494,22 @@ static int pk_enqueue(nmz_po_knn_plan *p, hipStream_t st, const uint64_t *d_q_of
         a.q_poff = p->q_poff, a.q_psym = p->q_psym, a.q_prof = p->q_prof, a.q_self = d_q_self;
         a.N = N, a.G = G, a.k = k, a.w = p->band;
         a.no_filter = (p->opts & NMZ_PO_KNN_OPT_NO_FILTER) ? 1u : 0u;
+        a.full_band = (p->opts & NMZ_PO_KNN_OPT_FULL_BAND) ? 1u : 0u;
         a.NB = (N + 63) / 64;
-        const uint64_t n_blocks = (uint64_t)n_queries * a.NB, cap = (uint64_t)std::max(ctx->n_cu, 1) * PK_WAVES_PER_CU;
+        const bool wide = p->band > NMZ_PO_KNN_MAX_BAND;  // K11w: the persistent unit is a workgroup of four waves
+        const uint64_t n_blocks = (uint64_t)n_queries * a.NB;
+        const uint64_t cap = wide ? pkw_resident(ctx, p->band) : (uint64_t)std::max(ctx->n_cu, 1) * PK_WAVES_PER_CU;
         a.parts = 1;  // fewer than PK_ITEMS_PER_WAVE blocks per wave: the blocks' survivors in parts
         if (!(p->opts & NMZ_PO_KNN_OPT_WHOLE_BLOCKS))
             a.parts = (uint32_t)std::min<uint64_t>(64, (PK_ITEMS_PER_WAVE * cap + n_blocks - 1) / n_blocks);
         a.n_items = n_blocks * a.parts;
         a.knn = d_keys, a.counters = p->counters, a.next = p->next, a.over = p->over;
         const unsigned blocks = (unsigned)std::min<uint64_t>(a.n_items, cap);
-        p->blocks = p->waves = blocks;  // the workgroup is the wave
-        {
+        p->blocks = blocks;
+        p->waves = wide ? blocks * AW_WAVES : blocks;  // K11b: the workgroup is the wave
+        if (wide) {
+            rc = pkw_launch(ctx, st, a, blocks);
+        } else {
             KernelTimer kt(ctx, st, "po_knn");
             switch (align_cells(p->band)) {
                 case 1: hipLaunchKernelGGL(k_po_knn<1>, dim3(blocks), dim3(64), 0, st, a); break;
@@ -605,6 +582,74 @@ static int pk_batches(const uint64_t *q_off, uint32_t n_queries, uint64_t max_qu
     return NMZ_OK;
 }
 
+// the body of the two plan creates: band_ok and `known` (the opts bits) are the entry point's
+static int pk_plan_create_call(PkBandCheck band_ok, uint32_t known, nmz_ctx *ctx, const uint64_t *off,
+                               const uint64_t *sym, const uint32_t *entity, uint32_t n_traces, uint32_t n_entities,
+                               uint32_t band, uint64_t max_queries, uint64_t max_query_elems, uint32_t opts,
+                               nmz_po_knn_plan **out) {
+    NMZ_CHECK(out != nullptr, "out is NULL");
+    *out = nullptr;
+    // the arguments first: they are checked without a device
+    NMZ_TRY(pk_plan_shape(band_ok, known, band, n_entities, max_queries, opts));
+    NMZ_TRY(pk_csr("store", "n_traces", off, sym, entity, n_traces, n_entities));
+    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
+    CtxGuard g(ctx);
+    NMZ_TRY(g.rc);
+    return pk_plan_create_locked(ctx, off, sym, entity, n_traces, n_entities, band, max_queries, max_query_elems, opts,
+                                 out);
+}
+
+// the body of the two one-shot forms
+static int pk_one_shot(PkBandCheck band_ok, nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym,
+                       const uint32_t *entity, uint32_t n_traces, uint32_t n_entities, const uint64_t *q_off,
+                       const uint64_t *q_sym, const uint32_t *q_entity, const uint32_t *q_self, uint32_t n_queries,
+                       uint32_t band, uint32_t k, uint32_t *knn_id, uint32_t *knn_dist) {
+    // the arguments first: they are checked without a device
+    NMZ_TRY(band_ok(band));
+    NMZ_TRY(pk_k(k));
+    NMZ_TRY(pk_entities(n_entities));
+    NMZ_TRY(pk_csr("store", "n_traces", off, sym, entity, n_traces, n_entities));
+    NMZ_TRY(pk_validate_queries(q_off, q_sym, q_entity, q_self, n_queries, n_traces, n_entities, knn_id, knn_dist));
+    if (n_queries == 0) return NMZ_OK;  // nothing to write: no device either
+    if (n_traces == 0) {                // nothing to find: no device either
+        std::fill(knn_id, knn_id + (size_t)n_queries * k, NMZ_NONE);
+        std::fill(knn_dist, knn_dist + (size_t)n_queries * k, NMZ_NONE);
+        return NMZ_OK;
+    }
+    std::vector<uint64_t> boff;
+    std::vector<uint32_t> bstart;
+    NMZ_TRY(pk_batches(q_off, n_queries, n_queries, q_off[n_queries], boff, bstart));
+    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
+    CtxGuard g(ctx);
+    NMZ_TRY(g.rc);
+    HostCall call(ctx);
+    nmz_po_knn_plan *plan = nullptr;
+    NMZ_TRY(pk_plan_create_locked(ctx, off, sym, entity, n_traces, n_entities, band, n_queries, q_off[n_queries], 0,
+                                  &plan));
+    call.own_plan<pk_plan_destroy_locked>(plan);
+    return pk_query_locked(plan, call, boff, bstart, q_off, q_sym, q_entity, q_self, n_queries, k, knn_id, knn_dist);
+}
+
+// the first n words of the latest search's counters, the stripes summed
+static int pk_counters(nmz_po_knn_plan *plan, uint64_t *out, uint32_t n, void *stream) {
+    NMZ_CHECK(plan != nullptr, "plan is NULL");
+    NMZ_CHECK(out != nullptr, "out is NULL");
+    CtxGuard g(plan->ctx);
+    NMZ_TRY(g.rc);
+    hipStream_t st = stream ? (hipStream_t)stream : plan->ctx->stream;
+    std::vector<uint64_t> h(ED_CNT_WORDS);
+    uint32_t over = 0;
+    NMZ_TRY(copy_d2h(h.data(), plan->counters, ED_CNT_WORDS, st));
+    NMZ_TRY(copy_d2h(&over, plan->over, 1, st));
+    NMZ_HIP(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; ++i) out[i] = 0;
+    for (uint32_t s = 0; s < ED_CNT_STRIPES; ++s)
+        for (uint32_t i = 0; i < n; ++i) out[i] += h[s * ED_CNT_LINE + i];
+    NMZ_CHECK(!over, "the latest search's query offsets did not start at 0, decreased or exceeded the plan's "
+                     "max_query_elems (" + std::to_string(plan->max_query_elems) + "): it wrote no list");
+    return NMZ_OK;
+}
+
 }  // namespace nmz
 
 using namespace nmz;
@@ -661,16 +706,17 @@ int nmz_po_knn_bound_host(const uint64_t *a, const uint32_t *ea, uint64_t n, con
 int nmz_po_knn_plan_create(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
                            uint32_t n_traces, uint32_t n_entities, uint32_t band, uint64_t max_queries,
                            uint64_t max_query_elems, uint32_t opts, nmz_po_knn_plan **out) {
-    NMZ_CHECK(out != nullptr, "out is NULL");
-    *out = nullptr;
-    // the arguments first: they are checked without a device
-    NMZ_TRY(pk_plan_shape(band, n_entities, max_queries, opts));
-    NMZ_TRY(pk_csr("store", "n_traces", off, sym, entity, n_traces, n_entities));
-    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
-    CtxGuard g(ctx);
-    NMZ_TRY(g.rc);
-    return pk_plan_create_locked(ctx, off, sym, entity, n_traces, n_entities, band, max_queries, max_query_elems, opts,
-                                 out);
+    return pk_plan_create_call(pk_band, PK_OPTS, ctx, off, sym, entity, n_traces, n_entities, band, max_queries,
+                               max_query_elems, opts, out);
+}
+
+// The same plan for every band 0 .. 1,024: a band above 64 searches with K11w (ed_po_knn_wide.hip), a band <= 64 with
+// K11b and so with the narrow entry point's bytes.
+int nmz_po_knn_wide_plan_create(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity,
+                                uint32_t n_traces, uint32_t n_entities, uint32_t band, uint64_t max_queries,
+                                uint64_t max_query_elems, uint32_t opts, nmz_po_knn_plan **out) {
+    return pk_plan_create_call(pkw_band, PKW_OPTS, ctx, off, sym, entity, n_traces, n_entities, band, max_queries,
+                               max_query_elems, opts, out);
 }
 
 int nmz_po_knn_plan_destroy(nmz_po_knn_plan *plan) {
@@ -718,49 +764,25 @@ int nmz_po_knn(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uin
                uint32_t n_entities, const uint64_t *q_off, const uint64_t *q_sym, const uint32_t *q_entity,
                const uint32_t *q_self, uint32_t n_queries, uint32_t band, uint32_t k, uint32_t *knn_id,
                uint32_t *knn_dist) {
-    // the arguments first: they are checked without a device
-    NMZ_TRY(pk_band(band));
-    NMZ_TRY(pk_k(k));
-    NMZ_TRY(pk_entities(n_entities));
-    NMZ_TRY(pk_csr("store", "n_traces", off, sym, entity, n_traces, n_entities));
-    NMZ_TRY(pk_validate_queries(q_off, q_sym, q_entity, q_self, n_queries, n_traces, n_entities, knn_id, knn_dist));
-    if (n_queries == 0) return NMZ_OK;  // nothing to write: no device either
-    if (n_traces == 0) {                // nothing to find: no device either
-        std::fill(knn_id, knn_id + (size_t)n_queries * k, NMZ_NONE);
-        std::fill(knn_dist, knn_dist + (size_t)n_queries * k, NMZ_NONE);
-        return NMZ_OK;
-    }
-    std::vector<uint64_t> boff;
-    std::vector<uint32_t> bstart;
-    NMZ_TRY(pk_batches(q_off, n_queries, n_queries, q_off[n_queries], boff, bstart));
-    NMZ_CHECK(ctx != nullptr, "ctx is NULL");
-    CtxGuard g(ctx);
-    NMZ_TRY(g.rc);
-    HostCall call(ctx);
-    nmz_po_knn_plan *plan = nullptr;
-    NMZ_TRY(pk_plan_create_locked(ctx, off, sym, entity, n_traces, n_entities, band, n_queries, q_off[n_queries], 0,
-                                  &plan));
-    call.own_plan<pk_plan_destroy_locked>(plan);
-    return pk_query_locked(plan, call, boff, bstart, q_off, q_sym, q_entity, q_self, n_queries, k, knn_id, knn_dist);
+    return pk_one_shot(pk_band, ctx, off, sym, entity, n_traces, n_entities, q_off, q_sym, q_entity, q_self, n_queries,
+                       band, k, knn_id, knn_dist);
+}
+
+int nmz_po_knn_wide(nmz_ctx *ctx, const uint64_t *off, const uint64_t *sym, const uint32_t *entity, uint32_t n_traces,
+                    uint32_t n_entities, const uint64_t *q_off, const uint64_t *q_sym, const uint32_t *q_entity,
+                    const uint32_t *q_self, uint32_t n_queries, uint32_t band, uint32_t k, uint32_t *knn_id,
+                    uint32_t *knn_dist) {
+    return pk_one_shot(pkw_band, ctx, off, sym, entity, n_traces, n_entities, q_off, q_sym, q_entity, q_self,
+                       n_queries, band, k, knn_id, knn_dist);
 }
 
 int nmz_po_knn_counters(nmz_po_knn_plan *plan, uint64_t *out, void *stream) {
-    NMZ_CHECK(plan != nullptr, "plan is NULL");
-    NMZ_CHECK(out != nullptr, "out is NULL");
-    CtxGuard g(plan->ctx);
-    NMZ_TRY(g.rc);
-    hipStream_t st = stream ? (hipStream_t)stream : plan->ctx->stream;
-    std::vector<uint64_t> h(ED_CNT_WORDS);
-    uint32_t over = 0;
-    NMZ_TRY(copy_d2h(h.data(), plan->counters, ED_CNT_WORDS, st));
-    NMZ_TRY(copy_d2h(&over, plan->over, 1, st));
-    NMZ_HIP(hipStreamSynchronize(st));
-    for (uint32_t i = 0; i < PK_NCOUNTERS; ++i) out[i] = 0;
-    for (uint32_t s = 0; s < ED_CNT_STRIPES; ++s)
-        for (uint32_t i = 0; i < PK_NCOUNTERS; ++i) out[i] += h[s * ED_CNT_LINE + i];
-    NMZ_CHECK(!over, "the latest search's query offsets did not start at 0, decreased or exceeded the plan's "
-                     "max_query_elems (" + std::to_string(plan->max_query_elems) + "): it wrote no list");
-    return NMZ_OK;
+    return pk_counters(plan, out, PK_NCOUNTERS, stream);
+}
+
+// Words 4 .. 8: the entity steps K11w ran at C = 1, 2, 3, 5, 9 cells per thread; K11b leaves them at 0.
+int nmz_po_knn_wide_counters(nmz_po_knn_plan *plan, uint64_t *out, void *stream) {
+    return pk_counters(plan, out, PKW_NCOUNTERS, stream);
 }
 
 }  // extern "C"

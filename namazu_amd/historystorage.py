@@ -239,17 +239,25 @@ class Naive(HistoryStorage):
         """SearchSimilar under the per-entity distance: the k nearest stored traces to `trace` (a SingleTrace carrying
         entities) by (ED^PO_band asc, id asc), as [(id, distance)]; a run that merely interleaved its independent
         entities differently is at 0. The stored runs are projected once and stay on the GPU (PoSimilarityIndex)
-        until the storage holds a different number of traces. band <= 64 (the library refuses wider ones)."""
+        until the storage holds a different number of traces. band <= 64 (the library refuses wider ones;
+        SearchSimilarPOWide takes them)."""
+        return self._search_similar_po(trace, k, band, wide=False)
+
+    def SearchSimilarPOWide(self, trace, k, band):
+        """SearchSimilarPO for every band 0 .. 1,024, through a wide PoSimilarityIndex (K11w above band 64)."""
+        return self._search_similar_po(trace, k, band, wide=True)
+
+    def _search_similar_po(self, trace, k, band, wide):
         if not isinstance(trace, SingleTrace):
             raise TypeError("SearchSimilarPO needs a SingleTrace carrying entities")
         n = self.NrStoredHistories()
-        key = (band, n)
+        key = (band, n, wide)
         if getattr(self, "_po_index_key", None) != key:
             if getattr(self, "_po_index", None) is not None:
                 self._po_index.close()
                 self._po_index = None
             ts, ent, names = po_entities(self.traces())
-            self._po_index = PoSimilarityIndex(ts, ent, band, names)
+            self._po_index = PoSimilarityIndex(ts, ent, band, names, wide=wide)
             self._po_index_key = key
         ids, ds = self._po_index.query([trace], k)
         return [(int(i), int(d)) for i, d in zip(ids[0], ds[0]) if i != _lib.NMZ_NONE]
@@ -261,14 +269,16 @@ class Naive(HistoryStorage):
         earlier or later. po=True: the neighbours still come from the exact SearchSimilar at `band`, but distance and
         script are the per-entity ones (edit_scripts_po: interleavings of independent entities vanish); a neighbour
         whose ED^PO exceeds the band is left out. `trace` must then be a SingleTrace carrying entities.
-        po_search=True (needs po=True, band <= 64): the neighbours come from SearchSimilarPO instead, so a run whose
-        exact distance exceeds the band is found when its ED^PO is within it."""
+        po_search=True (needs po=True): the neighbours come from SearchSimilarPO instead (SearchSimilarPOWide for
+        64 < band <= 1024), so a run whose exact distance exceeds the band is found when its ED^PO is within it."""
         if po_search and not po:
             raise ValueError("po_search=True needs po=True: the PO search goes with the per-entity scripts")
         if po and not isinstance(trace, SingleTrace):
             raise TypeError("DiffSimilar(po=True) needs a SingleTrace carrying entities")
         t = trace.symbols if isinstance(trace, SingleTrace) else np.asarray(trace, np.uint64)
-        search = self.SearchSimilarPO if po_search else self.SearchSimilar
+        search = self.SearchSimilar
+        if po_search:
+            search = self.SearchSimilarPO if band <= _lib.NMZ_PO_KNN_MAX_BAND else self.SearchSimilarPOWide
         near = [(i, d) for i, d in search(trace, k, band) if d <= band]
         if po:
             if not near:
@@ -303,8 +313,9 @@ class Naive(HistoryStorage):
         pairs; .top(k) ranks the symbols. po=True: the neighbours still come from the exact search at `band`, the
         scripts and the profile are the per-entity ones (move_profile_po), so events of independent entities that
         merely interleaved differently are not counted; pairs with ED^PO > band count as beyond. po_search=True
-        (needs po=True, band <= 64): a PoSimilarityIndex over the passing runs answers the failing runs' queries, so
-        the neighbours are the nearest passing runs by ED^PO, whatever their exact distance."""
+        (needs po=True): a PoSimilarityIndex over the passing runs (a wide one for 64 < band <= 1024) answers the
+        failing runs' queries, so the neighbours are the nearest passing runs by ED^PO, whatever their exact
+        distance."""
         if po_search and not po:
             raise ValueError("po_search=True needs po=True: the PO search goes with the per-entity profile")
         passing, failing = [], []
@@ -322,7 +333,7 @@ class Naive(HistoryStorage):
             raise ValueError("no passing run: nothing to contrast")
         if po_search:
             pts, pent, pnames = po_entities([t for _, t in passing])
-            index = PoSimilarityIndex(pts, pent, band, pnames, ctx=ctx)
+            index = PoSimilarityIndex(pts, pent, band, pnames, ctx=ctx, wide=band > _lib.NMZ_PO_KNN_MAX_BAND)
         else:
             index = SimilarityIndex(TraceSet([t.symbols for _, t in passing]), band, ctx=ctx)
         try:
@@ -1235,12 +1246,11 @@ def move_profile_po(ts, entity, pairs, band, ctx=None, usym=None, n_entities=Non
 
 
 # ---- PO k-NN search: the nearest stored runs by per-entity edit distance ---------------------------------------------
-def _po_knn_ctx(ctx, band, k, G, n_queries, n_traces):
+def _po_knn_ctx(ctx, band, k, G, n_queries, n_traces, max_band=_lib.NMZ_PO_KNN_MAX_BAND):
     """The context of a PO search: none where the library answers (or refuses) without a device."""
     if ctx is not None:
         return ctx
-    legal = (band <= _lib.NMZ_PO_KNN_MAX_BAND and 1 <= k <= _lib.NMZ_PO_KNN_MAX_K
-             and 1 <= G <= _lib.NMZ_PO_MAX_ENTITIES)
+    legal = band <= max_band and 1 <= k <= _lib.NMZ_PO_KNN_MAX_K and 1 <= G <= _lib.NMZ_PO_MAX_ENTITIES
     return _lib.default_context() if legal and n_queries and n_traces else None
 
 
@@ -1250,6 +1260,16 @@ def po_knn(ts, entity, queries_ts, q_entity, k, band, n_entities=None, q_self=No
     NMZ_NONE where fewer stored traces are eligible. entity / q_entity are parallel to ts.sym / queries_ts.sym, ids
     global to both (po_entities). q_self[Q]: the store index each query skips (NMZ_NONE for none); queries = the
     store with q_self = arange is the all-pairs k-NN. band <= 64, 1 <= k <= 64."""
+    return _po_knn(ts, entity, queries_ts, q_entity, k, band, n_entities, q_self, ctx, wide=False)
+
+
+def po_knn_wide(ts, entity, queries_ts, q_entity, k, band, n_entities=None, q_self=None, ctx=None):
+    """po_knn for every band 0 .. 1,024 (nmz_po_knn_wide): a band above 64 searches with K11w, a band <= 64 gives
+    po_knn's bytes."""
+    return _po_knn(ts, entity, queries_ts, q_entity, k, band, n_entities, q_self, ctx, wide=True)
+
+
+def _po_knn(ts, entity, queries_ts, q_entity, k, band, n_entities, q_self, ctx, wide):
     band, k = int(band), int(k)
     entity, G1 = _po_entity(int(ts.off[-1]), entity, n_entities)
     q_entity, G2 = _po_entity(int(queries_ts.off[-1]), q_entity, n_entities)
@@ -1262,11 +1282,12 @@ def po_knn(ts, entity, queries_ts, q_entity, k, band, n_entities=None, q_self=No
     shape = (Q, min(max(k, 0), _lib.NMZ_PO_KNN_MAX_K))
     ids = np.full(shape, _lib.NMZ_NONE, np.uint32)
     ds = np.full(shape, _lib.NMZ_NONE, np.uint32)
-    ctx = _po_knn_ctx(ctx, band, k, G, Q, len(ts))
-    _lib.check(_lib.load().nmz_po_knn(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym),
-                                      _lib.ptr(entity), len(ts), G, _lib.ptr(queries_ts.off),
-                                      _lib.ptr(queries_ts.sym), _lib.ptr(q_entity), _lib.ptr(q_self), Q, band, k,
-                                      _lib.ptr(ids), _lib.ptr(ds)))
+    ctx = _po_knn_ctx(ctx, band, k, G, Q, len(ts),
+                      _lib.NMZ_PO_KNN_WIDE_MAX_BAND if wide else _lib.NMZ_PO_KNN_MAX_BAND)
+    fn = _lib.load().nmz_po_knn_wide if wide else _lib.load().nmz_po_knn
+    _lib.check(fn(ctx.handle if ctx else None, _lib.ptr(ts.off), _lib.ptr(ts.sym), _lib.ptr(entity), len(ts), G,
+                  _lib.ptr(queries_ts.off), _lib.ptr(queries_ts.sym), _lib.ptr(q_entity), _lib.ptr(q_self), Q, band, k,
+                  _lib.ptr(ids), _lib.ptr(ds)))
     return ids, ds
 
 
@@ -1287,11 +1308,16 @@ class PoSimilarityIndex:
     """A stored TraceSet with its entities, projected and profiled once and resident on the GPU for the PO search
     (nmz_po_knn_plan). `names` are the store's entity names (po_entities): names[id]. A query's entities unknown to
     the store all map to the one spare id len(names), and the plan is made with n_entities = len(names) + 1: exact,
-    since the store holds nothing there and each such element costs its one DEL whichever unknown entity it has."""
+    since the store holds nothing there and each such element costs its one DEL whichever unknown entity it has.
+    wide=True makes the plan through nmz_po_knn_wide_plan_create: every band 0 .. 1,024 (K11w above 64),
+    NMZ_PO_KNN_OPT_FULL_BAND among the opts, and counters() with the five per-C entity-step counts."""
+
+    STEP_NAMES = ("steps_c1", "steps_c2", "steps_c3", "steps_c5", "steps_c9")
 
     def __init__(self, ts, entity, band, names=(), ctx=None, max_queries=256, max_query_elems=1 << 18, opts=0,
-                 n_entities=None):
+                 n_entities=None, wide=False):
         self.ts = ts
+        self.wide = bool(wide)
         self.band = int(band)
         self.names = list(names)
         self._ids = {e: i for i, e in enumerate(self.names)}
@@ -1300,7 +1326,8 @@ class PoSimilarityIndex:
         self.entity, _ = _po_entity(int(ts.off[-1]), entity, self.n_entities)
         self.opts = int(opts)
         self.max_queries = int(max_queries)
-        legal = self.band <= _lib.NMZ_PO_KNN_MAX_BAND and self.n_entities <= _lib.NMZ_PO_MAX_ENTITIES
+        max_band = _lib.NMZ_PO_KNN_WIDE_MAX_BAND if self.wide else _lib.NMZ_PO_KNN_MAX_BAND
+        legal = self.band <= max_band and self.n_entities <= _lib.NMZ_PO_MAX_ENTITIES
         self.ctx = ctx or (_lib.default_context() if legal else None)
         self.plan = None
         self._create(int(max_query_elems))
@@ -1308,7 +1335,8 @@ class PoSimilarityIndex:
     def _create(self, max_query_elems):
         self.close()
         plan = ctypes.c_void_p()
-        _lib.check(_lib.load().nmz_po_knn_plan_create(
+        create = _lib.load().nmz_po_knn_wide_plan_create if self.wide else _lib.load().nmz_po_knn_plan_create
+        _lib.check(create(
             self.ctx.handle if self.ctx else None, _lib.ptr(self.ts.off), _lib.ptr(self.ts.sym), _lib.ptr(self.entity),
             len(self.ts), self.n_entities, self.band, self.max_queries, max_query_elems, self.opts, ctypes.byref(plan)))
         self.plan = plan
@@ -1364,11 +1392,13 @@ class PoSimilarityIndex:
             ctypes.c_void_p(stream) if stream else None))
 
     def counters(self, stream=None):
-        """The latest search's work: {filtered, length_sum, dp, in_band} pair counts."""
-        out = np.zeros(_lib.NMZ_PO_KNN_NCOUNTERS, np.uint64)
-        _lib.check(_lib.load().nmz_po_knn_counters(self.plan, _lib.ptr(out),
-                                                   ctypes.c_void_p(stream) if stream else None))
-        return dict(zip(("filtered", "length_sum", "dp", "in_band"), (int(v) for v in out)))
+        """The latest search's work: {filtered, length_sum, dp, in_band} pair counts; with wide=True also
+        {steps_c1, steps_c2, steps_c3, steps_c5, steps_c9}, the entity steps run at that many cells per thread."""
+        names = ("filtered", "length_sum", "dp", "in_band") + (self.STEP_NAMES if self.wide else ())
+        out = np.zeros(len(names), np.uint64)
+        fn = _lib.load().nmz_po_knn_wide_counters if self.wide else _lib.load().nmz_po_knn_counters
+        _lib.check(fn(self.plan, _lib.ptr(out), ctypes.c_void_p(stream) if stream else None))
+        return dict(zip(names, (int(v) for v in out)))
 
     def close(self):
         if self.plan:
